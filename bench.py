@@ -11,10 +11,17 @@ gather of the column partitions to rank 0 and the on-device assembly of the full
 Volumes are resident in HBM before the timed region (sync_volumes is not timed).  The K timed
 frames run one after the other on one HIP stream -- what a synchronous VolumeRender.render user
 gets per frame (minus the D2H copy) -- so `value` / `ms_per_step` are the serial frame rate and
-`ms_per_step` >= the march kernel's own time.  A second, separately reported pass
-(`pipelined`, --pipelined-streams, default 2) issues independent frames of a movie round-robin on
-several streams so that one frame's tail overlaps the next frame's start; it is not `value`.
-Run: python bench.py [--gpus N --steps K --warmup W]; N>1 under torch.distributed.run.
+`ms_per_step` >= the march kernel's own time.  A plain run does this and no more: set up, W warm-up
+frames, K timed frames, the result line (`value`, `ms_per_step`, the configuration).
+--dump-outputs DIR writes the last timed frame as DIR/image.npy (dump_outputs below).
+--full adds what takes runs of its own and reports them apart from `value`: the counted launch
+(sample counts, chunk statistics, the roofline figures), a second pass (`pipelined`,
+--pipelined-streams, default 2) that issues independent frames of a movie round-robin on several
+streams so that one frame's tail overlaps the next frame's start, the movie passes (--movie), the
+frame's sha256, and the CPU baseline with the sampled-column parity of the frame (--no-cpu-baseline
+leaves those two out).
+Run: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]; N>1 under
+torch.distributed.run.
 """
 from __future__ import annotations
 
@@ -71,6 +78,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline figure, each in runs of its own: the counted launch "
+                         "(sample counts, chunk statistics, roofline), the pipelined pass, the movie passes, the "
+                         "frame's sha256, the CPU baseline with its sampled-column parity; without it only the "
+                         "timed frames run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed frames, write the last one's image as DIR/image.npy (float32 [3][W][H], "
+                         "what a caller of the timed path receives; over 60 MB: a fixed seeded sample of its values)")
     ap.add_argument("--volume", type=int, default=1024, help="V_shell edge (metric config: 1024); not --n, which torch.distributed.run would take for its own --nnodes")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
@@ -113,6 +128,8 @@ def main():
     ap.add_argument("--traffic-json", default=_latest_traffic_json(),
                     help="PMC-measured HBM bytes per launch of the march kernel (tools/profile_summary.py)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -178,7 +195,7 @@ def main():
     ra, keep = mex.render_args(lights, lut, np.float32([1.0, 0.4, 0.6]), np.float32([1, 1, 1]),
                                np.uint64([H, W]), np.flip(R, 0).astype(np.float32), np.float32([0, 3.0, 6.0]),
                                np.float32(0.9), np.float32([1, 1, 0]))
-    host_vol = vol_t.cpu().numpy() if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+    host_vol = vol_t.cpu().numpy() if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline) else None
     del vol_t, grads  # the library holds its own resident copies
 
     part = mex.partition(args.block_cols, rank, world) if world > 1 else None
@@ -198,8 +215,10 @@ def main():
         out_local = torch.zeros(3 * max_cols * H, dtype=torch.float32, device=dev)
     steps_t = torch.zeros(48, dtype=torch.int64, device=dev)
 
-    # sample count of this rank's launch (exact, counter variant; untimed)
-    mex.render_device(h, ra, out_local.data_ptr(), part, steps_t.data_ptr(), sptr)
+    # sample count of this rank's launch (exact, counter variant; untimed; --full, else the counts stay 0
+    # and are not reported)
+    if args.full:
+        mex.render_device(h, ra, out_local.data_ptr(), part, steps_t.data_ptr(), sptr)
     torch.cuda.synchronize(dev)
     my_samples = int(steps_t[0].item())
     my_lit = int(steps_t[1].item())
@@ -268,6 +287,8 @@ def main():
     elapsed = time.perf_counter() - t0
     kern_ms = [a.elapsed_time(b) for a, b in ev]
     t_kernel_s = sum(kern_ms) / len(kern_ms) / 1e3
+    if args.dump_outputs and rank == 0:  # the last timed frame (N > 1: assembled from the gathered parts)
+        dump_outputs(args.dump_outputs, (out_local if world == 1 else full)[: 3 * W * H].view(3, W, H))
     cdev = torch.device("cpu") if gloo else dev  # device of the small report tensors
     ranks = None
     if world > 1:  # per-rank kernel time and the per-frame time beyond it (the exposed gather +
@@ -283,7 +304,7 @@ def main():
 
     # ---- extra pass (not `value`): independent frames round-robin on several streams ----------
     pipe_elapsed = None
-    ns = args.pipelined_streams if not (world > 1 and gloo) else 0  # (the rehearsal skips this pass)
+    ns = args.pipelined_streams if (args.full and not (world > 1 and gloo)) else 0  # (the rehearsal skips this pass)
     if ns > 1:
         streams = [torch.cuda.Stream(dev) for _ in range(ns)]
         outs = [torch.zeros_like(out_local) for _ in range(ns)]
@@ -336,7 +357,7 @@ def main():
         del sim_out
 
     movies = None
-    if args.movie > 0 and world == 1:
+    if args.full and args.movie > 0 and world == 1:
         movies = movie_passes(args, mex, h, lights, lut, W, H, stream, sptr, dev, out_local.numel())
 
     samples_all = torch.tensor([my_samples, my_lit], dtype=torch.int64, device=cdev)
@@ -384,6 +405,10 @@ def main():
                        "frames": "serial, one HIP stream" + (
                            "; the gather of frame i overlapped with the render of frame i + 1"
                            if world > 1 and args.gather == "overlap" else "")},
+            "cpu_baseline": None,
+        }
+    if rank == 0 and args.full:  # what the counted launch and the kernel's own HIP-event time give
+        result.update({
             "samples_per_frame": total_samples,
             "shaded_samples_per_frame": total_lit,
             "chunks_staged_leaped_global": chunk_stats,
@@ -413,8 +438,8 @@ def main():
                                                    "1"},
                          "sample_stream_frac": round(achieved / HBM_PEAK_GBS, 4),
                          "valu": None},
-            "cpu_baseline": None,
-        }
+        })
+    if rank == 0:
         if pipe_elapsed is not None:
             result["pipelined"] = {"streams": ns, "ms_per_step": round(pipe_elapsed / args.steps * 1e3, 3),
                                    "mrays_s": round(rays * args.steps / pipe_elapsed / 1e6, 3),
@@ -435,7 +460,7 @@ def main():
             result["sim_parts_kernel_ms"] = {"parts": args.sim_parts, "per_part": sim, "max": max(sim),
                                              "est_speedup": round(t_kernel_s * 1e3 / max(sim), 2)}
 
-    if rank == 0:  # the frame's identity, also without the CPU baseline (A/B runs); at N > 1 the last
+    if rank == 0 and args.full:  # the frame's identity, also without the CPU baseline (A/B runs); at N > 1 the last
         # frame assembled from the gathered parts -- the same bytes as the one-GPU frame
         import hashlib
         img = out_local if world == 1 else full
@@ -447,7 +472,9 @@ def main():
         result["cpu_baseline"], result["parity_sampled_columns"] = cpu_baseline(
             args, host_vol, n, W, H, refl, lut, lights, R, full if world > 1 else out_local)
 
-    if rank == 0:
+    if rank == 0 and not args.full:
+        print(json.dumps(result), flush=True)
+    elif rank == 0:
         # roofline.traffic / .valu: per-launch HBM bytes and VALU instructions of the march kernel
         # from the rocprofv3 PMC passes committed under profiles/ (tools/profile_summary.py;
         # FETCH_SIZE x 2 KiB + WRITE_SIZE KiB, the x2 being the gfx950 64-B-per-128-B-request tally);
@@ -479,6 +506,25 @@ def main():
     vr.volumeRender("delete", h)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_MAX_FLOATS = 15_000_000  # --dump-outputs: 60 MB of float32, under the 64 MB a dump may take
+
+
+def dump_outputs(dirpath, img):
+    """--dump-outputs: the frame a caller of the timed path receives, as dirpath/image.npy -- the device
+    image [3][W][H] in float32, whole when it fits DUMP_MAX_FLOATS (the metric frame: 24.9 MB), else
+    its values at a fixed sample of flat indices (seed 0, ascending), the same for every run of a
+    given image size.  The inputs are synthetic and seedless, so two builds run with the same
+    arguments can be compared value for value."""
+    os.makedirs(dirpath, exist_ok=True)
+    flat = img.reshape(-1)
+    if flat.numel() > DUMP_MAX_FLOATS:
+        idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_MAX_FLOATS, replace=False))
+        arr = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+    else:
+        arr = img.cpu().numpy()
+    np.save(os.path.join(dirpath, "image.npy"), np.ascontiguousarray(arr, dtype=np.float32))
 
 
 def movie_passes(args, mex, h, lights, lut, W, H, stream, sptr, dev, out_floats):

@@ -264,6 +264,25 @@ def test_cpu_share_is_positive():
     assert 1 <= bench.cpu_share() <= (os.cpu_count() or 1)
 
 
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the frame whole as float32 [3][W][H]; an image over the size limit as
+    its values at one fixed (seeded) ascending sample of flat indices, the same in every run."""
+    import sys
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    img = torch.arange(3 * 7 * 5, dtype=torch.float32).view(3, 7, 5) * 0.5
+    bench.dump_outputs(str(tmp_path / "a"), img)
+    whole = np.load(tmp_path / "a" / "image.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, img.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_FLOATS", 40)
+    bench.dump_outputs(str(tmp_path / "b"), img)
+    bench.dump_outputs(str(tmp_path / "c"), img)
+    part = np.load(tmp_path / "b" / "image.npy")
+    assert part.dtype == np.float32 and part.shape == (40,) and np.array_equal(part, np.load(tmp_path / "c" / "image.npy"))
+    assert np.all(np.diff(part) > 0) and np.isin(part, img.numpy().reshape(-1)).all()
+
+
 def _gvec_brick_index(X, Y, Z, bx, by):
     """Entry of padded voxel (X, Y, Z) in the 2x2x2-brick lookup-gradient copy (vr_kernels.hip
     interleave3_kernel, DESIGN.md s5 "Lookup-gradient copy")."""

@@ -14,7 +14,7 @@ Steps ('|' separates variants, ',' environment assignments inside a variant):
                                  --height 768; '-' for none)
   abl:SCENES:NAME=LIB[;ENV,..]|..  tools/shade_ablation.py parity of shading variants on the scenes
                                  (c2, metric, c4_main, c4_struct)                  -> ablation.json
-  bench[:ARGS]                   the bench line (CPU baseline included unless ARGS say otherwise)
+  bench[:ARGS]                   the bench.py --full line (CPU baseline included unless ARGS say otherwise)
                                  -> bench.json (the N-th bench step of a pass: benchN.json)
   kt[:ARGS]                      rocprofv3 --kernel-trace --stats of bench.py      -> ktN/ (N-th kt)
   pmc[:[@K=V,..@]ARGS]           tools/pmc.sh counter passes (one group per pass)  -> pmcN/ (N-th pmc);
@@ -65,7 +65,8 @@ def step_ab(out, rest, idx, bench_args):
             e = dict(os.environ, VR_TEST_SWITCHES="1")  # (bench.py: the library reads the VR_* switches)
             e.update(env)
             res = os.path.join(out, f"ab{idx}_{name}_{r}.json")
-            cmd = [PY, "bench.py", "--steps", "20", "--warmup", "4", "--no-cpu-baseline", "--pipelined-streams", "0"]
+            cmd = [PY, "bench.py", "--full", "--steps", "20", "--warmup", "4", "--no-cpu-baseline",
+                   "--pipelined-streams", "0"]  # (--full: the kernel's own ms and the frame's sha256)
             with open(res, "wb") as fh:
                 rc = subprocess.run(["timeout", "-k", "10", "300"] + cmd + extra, cwd=ROOT, stdout=fh,
                                     stderr=subprocess.DEVNULL, env=e).returncode
@@ -119,8 +120,8 @@ def main():
             n_bench += 1
             tag = "bench" if n_bench == 1 else f"bench{n_bench}"
             with open(os.path.join(out, tag + ".json"), "wb") as fh, open(os.path.join(out, tag + ".err"), "wb") as fe:
-                rc = subprocess.run(["timeout", "-k", "10", "500", PY, "bench.py"] + shlex.split(rest), cwd=ROOT,
-                                    stdout=fh, stderr=fe).returncode
+                rc = subprocess.run(["timeout", "-k", "10", "500", PY, "bench.py", "--full"] + shlex.split(rest),
+                                    cwd=ROOT, stdout=fh, stderr=fe).returncode
             print(f"  {tag} rc={rc} ({rest or 'default'})", flush=True)
         elif kind == "kt":
             args = shlex.split(rest) or ["--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--pipelined-streams",
@@ -128,8 +129,8 @@ def main():
             e = dict(os.environ, TMPDIR="/tmp")
             n_kt += 1
             rc = run(["rocprofv3", "--kernel-trace", "--stats", "-d", os.path.join(out, f"kt{n_kt}"), "-o", "kt",
-                      "--output-format", "csv", "--", PY, "bench.py"] + args, os.path.join(out, f"kt{n_kt}.log"), 400,
-                     env=e)
+                      "--output-format", "csv", "--", PY, "bench.py", "--full"] + args,
+                     os.path.join(out, f"kt{n_kt}.log"), 400, env=e)
         elif kind == "pmc":
             n_pmc += 1
             penv = None
