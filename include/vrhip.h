@@ -8,7 +8,9 @@
  *
  * Conventions (identical to what the mex receives from MATLAB):
  *   - volumes are MATLAB single arrays Data(d0,d1,d2), column-major, d0 fastest; a 2-D array has
- *     d2 = 1 (volumeRender.cpp:320-339).  Data pointers are borrowed for the call only.
+ *     d2 = 1 (volumeRender.cpp:320-339).  Data pointers are borrowed for the call only.  Emission,
+ *     reflection and absorption data may also be uint8, uint16, int16 or binary16 (vr_dtype below):
+ *     converted exactly to single on the device during the upload.
  *   - the rendered image is MATLAB single [H, W, 3], column-major: out[x*H + y + c*W*H]
  *     (volumeRender_kernel.cu:496-506, render.cpp:248).
  *   - every function returns VR_OK (0) or an error code; vr_last_error() gives the message
@@ -36,16 +38,43 @@ enum vr_status {
 /* Where vr_volume.data lives. */
 enum vr_location { VR_HOST = 0, VR_DEVICE = 1 };
 
+/* Element type of vr_volume.data.  The resident volume is always fp32: a narrow volume crosses the
+ * host link in its own width and is widened on the device in the pad pass of the upload, so the
+ * resident buffer and every image are bit for bit what MATLAB's single(Data) gives.
+ *   - without VR_DTYPE_UNORM the resident voxel is the source element converted to fp32 -- exact
+ *     for all four narrow types; for VR_F16 (IEEE binary16) that includes subnormals, +-0, +-inf
+ *     and NaN (a NaN stays a NaN, its payload widened);
+ *   - with VR_DTYPE_UNORM (VR_U8 / VR_U16 only) it is one correctly rounded fp32 division of the
+ *     converted value by 255.0f resp. 65535.0f: MATLAB's single(x) / single(255).
+ * Typed volumes are for emission, reflection and absorption.  The illumination LUT and the
+ * gradient volumes dx, dy, dz must be VR_F32 (VR_ERR_UNSUPPORTED otherwise).  An unknown code, or
+ * VR_DTYPE_UNORM on anything but VR_U8 / VR_U16, and a data pointer not aligned to its element
+ * size, are VR_ERR_ARGUMENT.  The dtype is part of a volume's identity: two views of one buffer
+ * with different element types are different volumes. */
+enum vr_dtype { VR_F32 = 0, VR_U8 = 1, VR_U16 = 2, VR_I16 = 3, VR_F16 = 4 };
+#define VR_DTYPE_UNORM 0x100 /* VR_U8 / VR_U16 only: value = (float)x / 255.0f resp. 65535.0f */
+
 /* A MATLAB `Volume` as the mex reads it (mxMake_volume, volumeRender.cpp:307-342):
- * Data (single), its dims, and TimeLastUpdate.  `location` VR_DEVICE lets device-resident data
- * (e.g. a torch tensor) be synced without a host round trip. */
+ * Data, its dims, and TimeLastUpdate.  `location` VR_DEVICE lets device-resident data
+ * (e.g. a torch tensor) be synced without a host round trip.  `data` keeps its declared type; for
+ * dtype != VR_F32 it points to d0*d1*d2 elements of that type, column-major, on the host or the
+ * device per `location`.  A zero-initialised dtype is VR_F32 (MATLAB single). */
 typedef struct vr_volume {
   const float *data;
   uint64_t dims[3];      /* d0, d1, d2 (d2 = 1 for 2-D data)          */
   uint64_t last_update;  /* TimeLastUpdate (ms timestamp, see vr_timestamp) */
   int32_t location;      /* enum vr_location                           */
-  int32_t reserved;
+  int32_t dtype;         /* enum vr_dtype, optionally | VR_DTYPE_UNORM  */
 } vr_volume;
+
+/* Element size in bytes of a dtype code (flag included), or 0 for an invalid code or an invalid
+ * flag combination.  Needs no device. */
+size_t vr_dtype_size(int32_t dtype);
+
+/* The upload's conversion on the CPU (the contract above): dst[i] = fp32 of element i of src, for
+ * n elements.  VR_ERR_ARGUMENT for an invalid dtype, a NULL pointer with n > 0, or a src not
+ * aligned to its element size.  Needs no device. */
+int vr_convert_host(const void *src, int32_t dtype, uint64_t n, float *dst);
 
 /* A MATLAB `LightSource` (LightSource.m:40-64): Position and Color exactly as stored in MATLAB.
  * The position is reversed into kernel order internally (render.cpp:167-168). */

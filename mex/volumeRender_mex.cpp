@@ -29,12 +29,30 @@ void check(int rc) {
   if (rc != VR_OK) fail(rc);
 }
 
-// A MATLAB `Volume` object (Data single, TimeLastUpdate uint64), borrowed for this call.
+// A MATLAB `Volume` object (Data, TimeLastUpdate uint64), borrowed for this call.  Data is single,
+// or uint8 / uint16 / int16 (vr_dtype: widened to single on the device during the upload).  The
+// Volume class itself casts to single, so integer data comes from a RawVolume (mex/matlab/
+// RawVolume.m): when the object has a non-empty RawData it is taken instead of Data, with the
+// logical Unorm selecting single(x) / single(255 resp. 65535).
 vr_volume make_volume(const mxArray *obj) {
   const mxArray *data = mxGetPropertyShared(obj, 0, "Data");
   const mxArray *stamp = mxGetPropertyShared(obj, 0, "TimeLastUpdate");
-  if (!data || !mxIsSingle(data)) mexErrMsgTxt("Volume.Data must be single.");
+  const mxArray *raw = mxGetPropertyShared(obj, 0, "RawData");
+  bool unorm = false;
+  if (raw && mxGetNumberOfElements(raw) > 0) {
+    data = raw;
+    const mxArray *u = mxGetPropertyShared(obj, 0, "Unorm");
+    unorm = u && mxGetNumberOfElements(u) > 0 && mxGetScalar(u) != 0.0;
+  }
   vr_volume v{};
+  switch (data ? mxGetClassID(data) : mxUNKNOWN_CLASS) {
+    case mxSINGLE_CLASS: v.dtype = VR_F32; break;
+    case mxUINT8_CLASS: v.dtype = VR_U8; break;
+    case mxUINT16_CLASS: v.dtype = VR_U16; break;
+    case mxINT16_CLASS: v.dtype = VR_I16; break;
+    default: mexErrMsgTxt("Volume.Data must be single.");
+  }
+  if (unorm) v.dtype |= VR_DTYPE_UNORM;  // (the library rejects it on int16 / single)
   v.data = static_cast<const float *>(mxGetData(data));
   const mwSize nd = mxGetNumberOfDimensions(data);
   const mwSize *d = mxGetDimensions(data);

@@ -9,9 +9,10 @@ loudly if it has not been built -- there is no CPU fallback.
 from ._lib import VrError, lib
 from .mex import HenyeyGreenstein, set_clock, timestamp, volumeRender
 from .volume import LightSource, Volume
+from .raw_volume import RawVolume
 from .volume_render import StereoRenderMode, VolumeRender
 
 lib()  # fail at import time if libvrhip.so is missing
 
-__all__ = ["VolumeRender", "Volume", "LightSource", "StereoRenderMode", "volumeRender", "HenyeyGreenstein",
+__all__ = ["VolumeRender", "Volume", "RawVolume", "LightSource", "StereoRenderMode", "volumeRender", "HenyeyGreenstein",
            "timestamp", "set_clock", "VrError", "lib"]

@@ -16,11 +16,14 @@ LIB_PATH = os.environ.get("VR_LIB_PATH") or _DEFAULT_PATH  # override: A/B build
 VR_OK = 0
 VR_HOST = 0
 VR_DEVICE = 1
+# enum vr_dtype (include/vrhip.h): element type of VrVolume.data; VR_DTYPE_UNORM ORed onto U8 / U16
+VR_F32, VR_U8, VR_U16, VR_I16, VR_F16 = 0, 1, 2, 3, 4
+VR_DTYPE_UNORM = 0x100
 
 
 class VrVolume(ctypes.Structure):
     _fields_ = [("data", c_void_p), ("dims", c_uint64 * 3), ("last_update", c_uint64),
-                ("location", c_int32), ("reserved", c_int32)]
+                ("location", c_int32), ("dtype", c_int32)]
 
 
 class VrLight(ctypes.Structure):
@@ -77,6 +80,8 @@ SIGNATURES = [
     ("vr_sum_channels_device", c_int, [c_void_p, c_int32, c_int32, c_uint64, c_void_p, c_void_p]),
     ("vr_henyey_greenstein", c_int, [c_uint32, c_float, c_void_p]),
     ("vr_timestamp", c_uint64, []),
+    ("vr_dtype_size", c_size_t, [c_int32]),
+    ("vr_convert_host", c_int, [c_void_p, c_int32, c_uint64, c_void_p]),
     ("vr_render_device", c_int, [c_void_p, POINTER(VrRenderArgs), POINTER(VrPartition), c_void_p, c_void_p,
                                  c_void_p]),
     ("vr_render_stereo_device", c_int, [c_void_p, POINTER(VrRenderArgs), c_float, c_void_p, c_void_p, c_void_p,

@@ -195,10 +195,12 @@ struct VolRec {
   uint64_t memory_size = 0;
   uint64_t last_update = 0;
   int32_t location = VR_HOST;
+  int32_t dtype = VR_F32;  // element type of data (vr_dtype | VR_DTYPE_UNORM); the host never reads voxels
 };
-// operator== (volumeRender.cpp:24-26)
+// operator== (volumeRender.cpp:24-26); the element type is part of the identity: two views of one
+// buffer with different types are different volumes
 bool same(const VolRec &a, const VolRec &b) {
-  return a.data == b.data && a.last_update == b.last_update && a.memory_size == b.memory_size;
+  return a.data == b.data && a.last_update == b.last_update && a.memory_size == b.memory_size && a.dtype == b.dtype;
 }
 
 VolRec make_rec(const vr_volume *v) {
@@ -206,10 +208,26 @@ VolRec make_rec(const vr_volume *v) {
   if (!v) return r;
   r.data = v->data;
   for (int i = 0; i < 3; ++i) r.dims[i] = v->dims[i];
-  r.memory_size = v->dims[0] * v->dims[1] * v->dims[2] * sizeof(float);
+  r.memory_size = v->dims[0] * v->dims[1] * v->dims[2] * sizeof(float);  // the resident (fp32) size
   r.last_update = v->last_update;
   r.location = v->location;
+  r.dtype = v->dtype;
   return r;
+}
+
+// A volume argument's element type (include/vrhip.h vr_dtype): VR_OK, or the error of an invalid
+// code / flag combination or a data pointer not aligned to its element size; `fp32_only` for the
+// illumination LUT and the gradient volumes.
+int check_dtype(const vr_volume *v, bool fp32_only, const char *what) {
+  if (!v) return VR_OK;
+  const size_t es = vr::dtype_size(v->dtype);
+  if (!es) return fail(VR_ERR_ARGUMENT, std::string(what) + ": invalid dtype");
+  if (fp32_only && v->dtype != VR_F32)
+    return fail(VR_ERR_UNSUPPORTED, std::string(what) + ": must be fp32 (typed volumes are for emission, reflection "
+                                                       "and absorption)");
+  if (reinterpret_cast<uintptr_t>(v->data) % es)
+    return fail(VR_ERR_ARGUMENT, std::string(what) + ": data is not aligned to its element size");
+  return VR_OK;
 }
 
 // A device-resident volume (the cudaArray analog): fp32 in HBM in the apron layout of
@@ -222,9 +240,11 @@ struct DevBuf {
   bool nonfinite = false;
   float maxabs = 0.f;
   uint64_t version = 0;  // bumped by every upload into this buffer
-  // the MATLAB Volume it was uploaded from (VolRec identity: data pointer, TimeLastUpdate, size)
+  // the MATLAB Volume it was uploaded from (VolRec identity: data pointer, TimeLastUpdate, size,
+  // element type)
   const float *src_data = nullptr;
   uint64_t src_last_update = 0, src_bytes = 0;
+  int32_t src_dtype = VR_F32;
   // completions of the launches / peer copies that read it (vr_resources.h): it is neither
   // rewritten nor freed before all of them
   vr_host::Readers readers;
@@ -488,8 +508,8 @@ void sync_volume(vr_context *h, int tex, int slot) {
     vr_host::Uploader &U = vr_host::uploaders()[h->device];
     VR_HIP(U.init(h->device));
     vr::BufStats st{0u, 0.f};
-    VR_HIP(U.upload(v.data, v.location == VR_DEVICE, (int32_t)v.dims[0], (int32_t)v.dims[1], (int32_t)v.dims[2],
-                    b->ptr, &st));
+    VR_HIP(U.upload(v.data, v.dtype, v.location == VR_DEVICE, (int32_t)v.dims[0], (int32_t)v.dims[1],
+                    (int32_t)v.dims[2], b->ptr, &st));
     b->nonfinite = st.nonfinite != 0;
     b->maxabs = st.maxabs;
     if (tex == T_LIGHT) build_zpair(b.get(), U.stream);
@@ -501,6 +521,7 @@ void sync_volume(vr_context *h, int tex, int slot) {
   b->src_data = v.data;
   b->src_last_update = v.last_update;
   b->src_bytes = v.memory_size;
+  b->src_dtype = v.dtype;
   h->buf[slot] = b;
   g_tex.bind[tex] = b;
 }
@@ -515,7 +536,8 @@ void sync_volume_if_changed(vr_context *h, int tex, int slot) {
   const BufPtr &b = g_tex.bind[tex];
   const VolRec &v = h->vol[slot];
   if (b && h->buf[slot] == b && b->device == h->device && v.data && b->src_data == v.data &&
-      b->src_last_update == v.last_update && b->src_bytes == v.memory_size && v.last_update != 0 &&
+      b->src_last_update == v.last_update && b->src_bytes == v.memory_size && b->src_dtype == v.dtype &&
+      v.last_update != 0 &&
       !env_flag("VR_ALWAYS_REUPLOAD"))
     return;
   sync_volume(h, tex, slot);
@@ -1317,6 +1339,8 @@ int do_render(vr_context *h, const vr_render_args *a, const vr_partition *part, 
               const float *eye2 = nullptr, int *fusable = nullptr) {
   if (fusable) *fusable = 0;
   if (a->num_lights > 0 && !a->lights) return fail(VR_ERR_ARGUMENT, "lights is NULL");
+  if (a->num_lights >= 0)
+    if (int rc = check_dtype(a->illumination, true, "illumination volume")) return rc;
   uint64_t required = required_memory(h);
   if (a->num_lights >= 0 && a->illumination) {
     required += a->illumination->dims[0] * a->illumination->dims[1] * a->illumination->dims[2] * 4 +
@@ -1564,6 +1588,8 @@ int do_render_slab(vr_context *h, const vr_render_args *a, const vr_slab *sl, co
   if (sl->depth == 0 || sl->z_first >= sl->depth || (sl->direction < -1 || sl->direction > 1))
     return fail(VR_ERR_ARGUMENT, "invalid slab");
   if (a->num_lights > 0 && !a->lights) return fail(VR_ERR_ARGUMENT, "lights is NULL");
+  if (a->num_lights >= 0)
+    if (int rc = check_dtype(a->illumination, true, "illumination volume")) return rc;
   upload_lights(h, a);
   int rc = build_frame(h, a, F, sl->depth);
   if (rc) return rc;
@@ -1740,6 +1766,7 @@ BufPtr replicate(const BufPtr &b, int dev, hipStream_t s, bool peer = true) {
   r->src_data = b->src_data;
   r->src_last_update = b->src_last_update;
   r->src_bytes = b->src_bytes;
+  r->src_dtype = b->src_dtype;
   r->version = next_version();
   b->replica_of[dev] = b->version;
   return r;
@@ -2009,6 +2036,13 @@ void resize_contributions(uint64_t in_len, uint64_t out_len, std::vector<double>
   }
 }
 
+// vr_convert_host: the upload's conversion (vr_convert.h) over a host array
+template <class T, bool UNORM>
+void convert_host(const void *src, uint64_t n, float *dst) {
+  const T *s = static_cast<const T *>(src);
+  for (uint64_t i = 0; i < n; ++i) dst[i] = vr::to_f32<UNORM>(s[i]);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2196,6 +2230,8 @@ static int do_sync_volumes(vr_context *h, uint64_t time_last_mem_sync, const vr_
   for (const vr_volume *v : {emission, reflection, absorption, lookup ? dx : nullptr, lookup ? dy : nullptr,
                              lookup ? dz : nullptr}) {
     if (!v) continue;
+    const bool grad = v == dx || v == dy || v == dz;
+    if (int rc = check_dtype(v, grad, grad ? "gradient volume" : "volume")) return rc;
     const uint64_t n = v->dims[0] * v->dims[1] * v->dims[2];
     if (n && !v->data) return fail(VR_ERR_ARGUMENT, "volume data is NULL");
     if (v->dims[0] > 0x7FFFFFFF || v->dims[1] > 0x7FFFFFFF || v->dims[2] > 0x7FFFFFFF)
@@ -2852,6 +2888,31 @@ int vr_henyey_greenstein(uint32_t n, float g, float *out) {
         out[(size_t)c * page + (size_t)a * n + b] = 1.f / (4.f * HG_PI) * (num / den);
       }
     }
+  }
+  return VR_OK;
+}
+
+// ---- typed volumes: the value contract on the host (no device needed) ---------------------------
+static_assert(vr::DT_F32 == VR_F32 && vr::DT_U8 == VR_U8 && vr::DT_U16 == VR_U16 && vr::DT_I16 == VR_I16 &&
+                  vr::DT_F16 == VR_F16 && vr::DT_UNORM == VR_DTYPE_UNORM,
+              "vr_convert.h codes = include/vrhip.h vr_dtype");
+
+size_t vr_dtype_size(int32_t dtype) { return vr::dtype_size(dtype); }
+
+int vr_convert_host(const void *src, int32_t dtype, uint64_t n, float *dst) {
+  const size_t es = vr::dtype_size(dtype);
+  if (!es) return fail(VR_ERR_ARGUMENT, "vr_convert_host: invalid dtype");
+  if (n && (!src || !dst)) return fail(VR_ERR_ARGUMENT, "vr_convert_host: NULL pointer");
+  if (reinterpret_cast<uintptr_t>(src) % es)
+    return fail(VR_ERR_ARGUMENT, "vr_convert_host: src is not aligned to its element size");
+  switch (dtype) {
+    case VR_F32: convert_host<float, false>(src, n, dst); break;
+    case VR_U8: convert_host<uint8_t, false>(src, n, dst); break;
+    case VR_U8 | VR_DTYPE_UNORM: convert_host<uint8_t, true>(src, n, dst); break;
+    case VR_U16: convert_host<uint16_t, false>(src, n, dst); break;
+    case VR_U16 | VR_DTYPE_UNORM: convert_host<uint16_t, true>(src, n, dst); break;
+    case VR_I16: convert_host<int16_t, false>(src, n, dst); break;
+    case VR_F16: convert_host<vr::half_bits, false>(src, n, dst); break;
   }
   return VR_OK;
 }

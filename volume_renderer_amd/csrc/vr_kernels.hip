@@ -23,6 +23,7 @@
 #include <stdint.h>
 #include <math.h>
 
+#include "vr_convert.h"
 #include "vr_device.h"
 #include "vr_sampling.h"
 
@@ -225,7 +226,12 @@ __global__ __launch_bounds__(256) void pad_volume_kernel(const float *__restrict
 // read of the source row, a coalesced write of the padded row with its two border copies; the
 // statistics of the written values (nonfinite flag, max |x| -- border copies repeat interior
 // values, so they change neither) are folded in on the way (the upload path, vr_resources.h).
-__global__ __launch_bounds__(256) void pad_planes_kernel(const float *__restrict__ src, int64_t z0, int32_t nx,
+// T is the source element type (vr_convert.h; float: a plain copy): a typed volume is widened here,
+// so the statistics are those of the converted values -- a half inf / NaN raises `nonfinite` as its
+// fp32 twin does.  One element per lane: the pass is bound by its 4-byte stores, the narrow loads
+// (1-2 bytes per voxel, coalesced at any row offset) move less than the fp32 ones.
+template <class T, bool UNORM>
+__global__ __launch_bounds__(256) void pad_planes_kernel(const T *__restrict__ src, int64_t z0, int32_t nx,
                                                          int32_t ny, int32_t nz, float *__restrict__ dst, int64_t k0,
                                                          uint64_t rows, BufStats *st) {
   const uint64_t px = (uint64_t)nx + 2, py = (uint64_t)ny + 2;
@@ -237,11 +243,11 @@ __global__ __launch_bounds__(256) void pad_planes_kernel(const float *__restrict
     const int64_t kk = (int64_t)k - 1, jj = j - 1;
     const int64_t sk = (kk < 0 ? 0 : (kk > (int64_t)nz - 1 ? (int64_t)nz - 1 : kk)) - z0;
     const int64_t sj = jj < 0 ? 0 : (jj > (int64_t)ny - 1 ? (int64_t)ny - 1 : jj);
-    const float *s = src + ((uint64_t)sk * (uint64_t)ny + (uint64_t)sj) * (uint64_t)nx;
+    const T *s = src + ((uint64_t)sk * (uint64_t)ny + (uint64_t)sj) * (uint64_t)nx;
     float *d = dst + (k * py + (uint64_t)j) * px;
     for (uint32_t i = threadIdx.x; i < px; i += blockDim.x) {
       const uint32_t si = i == 0 ? 0u : (i > (uint32_t)nx ? (uint32_t)nx - 1 : i - 1);
-      const float v = s[si];
+      const float v = to_f32<UNORM>(s[si]);
       d[i] = v;
       if (!(fabsf(v) <= 3.4028234e38f)) bad = 1;
       else mx = fmaxf(mx, fabsf(v));
@@ -592,14 +598,31 @@ hipError_t launch_pad(const float *src, float *dst, int32_t nx, int32_t ny, int3
   return hipGetLastError();
 }
 
-hipError_t launch_pad_planes(const float *src, int64_t z0, int32_t nx, int32_t ny, int32_t nz, float *dst, int64_t k0,
-                             int64_t k1, BufStats *st, hipStream_t s) {
+template <class T, bool UNORM>
+static void launch_pad_planes_t(const void *src, int64_t z0, int32_t nx, int32_t ny, int32_t nz, float *dst, int64_t k0,
+                                uint64_t rows, uint64_t blocks, BufStats *st, hipStream_t s) {
+  hipLaunchKernelGGL((pad_planes_kernel<T, UNORM>), dim3((unsigned)blocks), dim3(256), 0, s,
+                     static_cast<const T *>(src), z0, nx, ny, nz, dst, k0, rows, st);
+}
+
+// src: elements of `dtype` (vr_convert.h codes = include/vrhip.h vr_dtype | VR_DTYPE_UNORM)
+hipError_t launch_pad_planes(const void *src, int32_t dtype, int64_t z0, int32_t nx, int32_t ny, int32_t nz, float *dst,
+                             int64_t k0, int64_t k1, BufStats *st, hipStream_t s) {
   const uint64_t rows = (uint64_t)(k1 - k0) * ((uint64_t)ny + 2);
   if (!rows || nx <= 0 || ny <= 0 || nz <= 0) return hipSuccess;
   // a few workgroups per CU that loop over rows: few dispatches, so an upload that runs beside a
   // render (which holds most CU slots) is not held back by workgroup dispatch
   const uint64_t blocks = rows < 2048 ? rows : 2048;
-  hipLaunchKernelGGL(pad_planes_kernel, dim3((unsigned)blocks), dim3(256), 0, s, src, z0, nx, ny, nz, dst, k0, rows, st);
+  switch (dtype) {
+    case DT_F32: launch_pad_planes_t<float, false>(src, z0, nx, ny, nz, dst, k0, rows, blocks, st, s); break;
+    case DT_U8: launch_pad_planes_t<uint8_t, false>(src, z0, nx, ny, nz, dst, k0, rows, blocks, st, s); break;
+    case DT_U8 | DT_UNORM: launch_pad_planes_t<uint8_t, true>(src, z0, nx, ny, nz, dst, k0, rows, blocks, st, s); break;
+    case DT_U16: launch_pad_planes_t<uint16_t, false>(src, z0, nx, ny, nz, dst, k0, rows, blocks, st, s); break;
+    case DT_U16 | DT_UNORM: launch_pad_planes_t<uint16_t, true>(src, z0, nx, ny, nz, dst, k0, rows, blocks, st, s); break;
+    case DT_I16: launch_pad_planes_t<int16_t, false>(src, z0, nx, ny, nz, dst, k0, rows, blocks, st, s); break;
+    case DT_F16: launch_pad_planes_t<half_bits, false>(src, z0, nx, ny, nz, dst, k0, rows, blocks, st, s); break;
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 

@@ -12,7 +12,9 @@
 //     the launch's own stream -- never a global buffer rewritten under a running kernel;
 //   - Uploader: the upload path: persistent per-device copy and pad streams
 //     and a device staging ring; a host volume crosses PCIe in plane chunks, each padded into the
-//     apron layout (and its statistics taken) on the device while the next chunks copy.
+//     apron layout (and its statistics taken) on the device while the next chunks copy.  A typed
+//     volume (include/vrhip.h vr_dtype) crosses in its own element width -- staging slots, chunk
+//     thresholds and copy sizes are in source bytes -- and is widened to fp32 by the pad.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -30,11 +32,12 @@
 #include <thread>
 #include <vector>
 
+#include "vr_convert.h"
 #include "vr_device.h"
 
 namespace vr {
-hipError_t launch_pad_planes(const float *src, int64_t z0, int32_t nx, int32_t ny, int32_t nz, float *dst, int64_t k0,
-                             int64_t k1, BufStats *st, hipStream_t s);
+hipError_t launch_pad_planes(const void *src, int32_t dtype, int64_t z0, int32_t nx, int32_t ny, int32_t nz, float *dst,
+                             int64_t k0, int64_t k1, BufStats *st, hipStream_t s);
 }
 
 namespace vr_host {
@@ -504,8 +507,8 @@ struct Uploader {
   hipStream_t stream = nullptr;      // copies
   hipStream_t pad_stream = nullptr;  // pads + statistics
   hipEvent_t copied[NS] = {}, padded[NS] = {};
-  float *staging = nullptr;  // nslots slots of slot_floats
-  size_t slot_floats = 0, nslots = 0;
+  char *staging = nullptr;  // nslots slots of slot_bytes (source bytes: a typed volume's are narrow)
+  size_t slot_bytes = 0, nslots = 0;
   vr::BufStats *d_stats = nullptr, *h_stats = nullptr;
   Bounce bounce;  // VR_UPLOAD_BOUNCE=1: host sources through the pinned ring
 
@@ -530,35 +533,37 @@ struct Uploader {
     return rc;
   }
 
-  hipError_t ensure_staging(size_t floats) {
-    if (floats <= slot_floats) return hipSuccess;
+  hipError_t ensure_staging(size_t bytes) {
+    bytes = (bytes + 15) & ~(size_t)15;  // every slot starts 16-byte aligned, whatever the element size
+    if (bytes <= slot_bytes) return hipSuccess;
     nslots = 0;
     if (staging) (void)hipFree(staging);  // both upload streams are idle between uploads
     staging = nullptr;
-    slot_floats = 0;
-    const size_t slots = floats * sizeof(float) >= WHOLE / 2 ? 1 : NS;  // whole-volume staging: one slot
-    hipError_t rc = device_alloc(reinterpret_cast<void **>(&staging), slots * floats * sizeof(float));
+    slot_bytes = 0;
+    const size_t slots = bytes >= WHOLE / 2 ? 1 : NS;  // whole-volume staging: one slot
+    hipError_t rc = device_alloc(reinterpret_cast<void **>(&staging), slots * bytes);
     if (rc == hipSuccess) {
-      slot_floats = floats;
+      slot_bytes = bytes;
       nslots = slots;
     }
     return rc;
   }
 
   // src (host or device, per `on_device`) -> dst (padded, (nx+2)(ny+2)(nz+2) floats); *st = stats
-  static bool timing() {
-    static const bool on = [] {
-      const char *ev = vr::test_switches_on() ? std::getenv("VR_UPLOAD_TIMING") : nullptr;
-      return ev && ev[0] == '1';
-    }();
-    return on;
+  static bool timing() {  // read per call, like every other gated switch (a tool toggles it)
+    const char *ev = vr::test_switches_on() ? std::getenv("VR_UPLOAD_TIMING") : nullptr;
+    return ev && ev[0] == '1';
   }
   static double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
   }
 
-  hipError_t upload(const float *src, bool on_device, int32_t nx, int32_t ny, int32_t nz, float *dst,
+  hipError_t upload(const void *src_v, int32_t dtype, bool on_device, int32_t nx, int32_t ny, int32_t nz, float *dst,
                     vr::BufStats *st) {
+    const char *src = static_cast<const char *>(src_v);
+    const uint64_t esize = vr::dtype_size(dtype);  // source element size in bytes
+    if (!esize) return hipErrorInvalidValue;
+    const bool timed = timing();
     const double t0 = now_ms();
     double t_copied = t0;
     hipError_t rc = hipMemsetAsync(d_stats, 0, sizeof(vr::BufStats), pad_stream);
@@ -570,38 +575,40 @@ struct Uploader {
       EventPtr ev;
       rc = record_event(nullptr, ev);
       if (rc == hipSuccess) rc = hipStreamWaitEvent(pad_stream, ev->e, 0);
-      if (rc == hipSuccess) rc = vr::launch_pad_planes(src, 0, nx, ny, nz, dst, 0, (int64_t)nz + 2, d_stats, pad_stream);
+      if (rc == hipSuccess)
+        rc = vr::launch_pad_planes(src, dtype, 0, nx, ny, nz, dst, 0, (int64_t)nz + 2, d_stats, pad_stream);
     } else if (rc == hipSuccess) {
       // up to WHOLE bytes the volume crosses in one copy and is padded once it has landed: a pad
       // that runs beside a render in flight (the previous frame's) is slow, and between chunks it
       // would hold up the copies (measured: 1024^3 movie 98 ms per frame chunked vs 82 whole)
-      const uint64_t bytes = plane * (uint64_t)nz * sizeof(float);
+      const uint64_t bytes = plane * (uint64_t)nz * esize;
       uint64_t chunk = bytes <= WHOLE ? bytes : CHUNK;
       if (const char *ev = std::getenv("VR_UPLOAD_CHUNK_MB")) chunk = std::max<uint64_t>(1, std::strtoull(ev, nullptr, 10)) << 20;
-      const uint64_t per = std::max<uint64_t>(1, chunk / (plane * sizeof(float)));
+      const uint64_t per = std::max<uint64_t>(1, chunk / (plane * esize));
       const uint64_t chunk_planes = std::min<uint64_t>(per, (uint64_t)nz);
-      rc = ensure_staging(chunk_planes * plane);
+      rc = ensure_staging(chunk_planes * plane * esize);
       for (uint64_t z0 = 0, c = 0; rc == hipSuccess && z0 < (uint64_t)nz; z0 += chunk_planes, ++c) {
         const uint64_t z1 = std::min<uint64_t>((uint64_t)nz, z0 + chunk_planes);
         const int k = (int)(c % nslots);
-        float *slot = staging + (size_t)k * slot_floats;
+        char *slot = staging + (size_t)k * slot_bytes;
         if (c >= nslots) rc = hipStreamWaitEvent(stream, padded[k], 0);  // the slot's previous chunk is padded
         if (rc == hipSuccess) {
-          const size_t nbytes = (z1 - z0) * plane * sizeof(float);
-          if (use_bounce() && bounce.init() == hipSuccess) rc = bounce.copy(slot, src + z0 * plane, nbytes, stream);
-          else rc = hipMemcpyAsync(slot, src + z0 * plane, nbytes, hipMemcpyHostToDevice, stream);
+          const size_t nbytes = (z1 - z0) * plane * esize;
+          if (use_bounce() && bounce.init() == hipSuccess) rc = bounce.copy(slot, src + z0 * plane * esize, nbytes, stream);
+          else rc = hipMemcpyAsync(slot, src + z0 * plane * esize, nbytes, hipMemcpyHostToDevice, stream);
         }
         if (rc == hipSuccess) rc = hipEventRecord(copied[k], stream);
         if (rc == hipSuccess) rc = hipStreamWaitEvent(pad_stream, copied[k], 0);
         // padded planes: source plane z sits at z + 1; the apron planes 0 and nz + 1 replicate the ends
         const int64_t k0 = z0 == 0 ? 0 : (int64_t)z0 + 1;
         const int64_t k1 = z1 == (uint64_t)nz ? (int64_t)nz + 2 : (int64_t)z1 + 1;
-        if (rc == hipSuccess) rc = vr::launch_pad_planes(slot, (int64_t)z0, nx, ny, nz, dst, k0, k1, d_stats, pad_stream);
+        if (rc == hipSuccess)
+          rc = vr::launch_pad_planes(slot, dtype, (int64_t)z0, nx, ny, nz, dst, k0, k1, d_stats, pad_stream);
         if (rc == hipSuccess) rc = hipEventRecord(padded[k], pad_stream);
       }
     }
     if (rc == hipSuccess) rc = hipMemcpyAsync(h_stats, d_stats, sizeof(vr::BufStats), hipMemcpyDeviceToHost, pad_stream);
-    if (rc == hipSuccess && timing()) {  // diagnostics: when the copies and the pads ended
+    if (rc == hipSuccess && timed) {  // diagnostics: when the copies and the pads ended
       hipEvent_t ce = nullptr;
       if (hipEventCreate(&ce) == hipSuccess && hipEventRecord(ce, stream) == hipSuccess) {
         (void)hipEventSynchronize(ce);
@@ -611,9 +618,9 @@ struct Uploader {
     }
     if (rc == hipSuccess) rc = hipStreamSynchronize(pad_stream);  // the last pad followed the last copy
     if (rc == hipSuccess) rc = hipStreamSynchronize(stream);
-    if (rc == hipSuccess && timing())
+    if (rc == hipSuccess && timed)
       std::fprintf(stderr, "VR_UPLOAD_TIMING bytes %llu copies %.2f ms total %.2f ms\n",
-                   (unsigned long long)(plane * (uint64_t)nz * sizeof(float)), t_copied - t0, now_ms() - t0);
+                   (unsigned long long)(plane * (uint64_t)nz * esize), t_copied - t0, now_ms() - t0);
     if (rc == hipSuccess) *st = *h_stats;
     return rc;
   }

@@ -61,25 +61,69 @@ def _matlab_dims(a: np.ndarray):
     raise ValueError("volumes must have at most 3 dimensions")
 
 
+# numpy element types a volume may have -> vr_dtype (include/vrhip.h): converted exactly to fp32 on
+# the device during the upload
+_NP_DTYPES = {np.dtype(np.float32): _lib.VR_F32, np.dtype(np.uint8): _lib.VR_U8, np.dtype(np.uint16): _lib.VR_U16,
+              np.dtype(np.int16): _lib.VR_I16, np.dtype(np.float16): _lib.VR_F16}
+
+
+def dtype_code(np_dtype, unorm: bool = False) -> int:
+    """The vr_dtype code of a numpy element type (| VR_DTYPE_UNORM if `unorm`: uint8 / uint16 only,
+    value = single(x) / single(255 resp. 65535)); TypeError for a type volumes cannot have."""
+    code = _NP_DTYPES.get(np.dtype(np_dtype))
+    if code is None:
+        raise TypeError(f"volume data must be float32, uint8, uint16, int16 or float16, not {np.dtype(np_dtype)}")
+    return code | (_lib.VR_DTYPE_UNORM if unorm else 0)
+
+
+def dtype_size(code: int) -> int:
+    """vr_dtype_size: element size in bytes of a dtype code, 0 if the code is invalid."""
+    return int(lib().vr_dtype_size(int(code)))
+
+
+def convert_host(src: np.ndarray, unorm: bool = False, code=None) -> np.ndarray:
+    """vr_convert_host: the upload's element -> fp32 conversion on the CPU (same shape and order)."""
+    src = np.asarray(src)
+    code = dtype_code(src.dtype, unorm) if code is None else int(code)
+    flat = np.ascontiguousarray(src.reshape(-1, order="F"))
+    out = np.empty(flat.size, np.float32)
+    check(lib().vr_convert_host(flat.ctypes.data_as(ctypes.c_void_p), code, flat.size,
+                                out.ctypes.data_as(ctypes.c_void_p)))
+    return out.reshape(src.shape, order="F")
+
+
 class DeviceVolume:
     """A Volume whose Data already lives in HBM (e.g. a torch tensor on cuda): MATLAB-shaped dims
-    (d0, d1, d2), column-major fp32 at device address `ptr`.  Synced device-to-device."""
+    (d0, d1, d2), column-major at device address `ptr`, elements of `dtype` (a vr_dtype code; fp32
+    by default).  Synced device-to-device."""
 
-    def __init__(self, ptr: int, dims, last_update=None, owner=None):
+    def __init__(self, ptr: int, dims, last_update=None, owner=None, dtype=_lib.VR_F32):
         self.ptr = int(ptr)
+        self.dtype = int(dtype)
         d = tuple(int(x) for x in dims) + (1,) * (3 - len(dims))
         self.dims = d[:3]
         self.TimeLastUpdate = timestamp() if last_update is None else np.uint64(last_update)
         self.owner = owner  # keeps the backing allocation alive
 
     @classmethod
-    def from_tensor(cls, t, dims=None, last_update=None):
-        """`t` is a contiguous float32 cuda tensor holding the column-major data."""
+    def from_tensor(cls, t, dims=None, last_update=None, unorm=False):
+        """`t` is a contiguous cuda tensor holding the column-major data: float32, or uint8, int16,
+        float16 (and uint16 where the installed torch has it), widened to fp32 by the upload.
+        `unorm` (uint8 / uint16 only): voxel = single(x) / single(255 resp. 65535)."""
         import torch
-        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-            raise TypeError("DeviceVolume needs a contiguous float32 cuda tensor")
+        codes = {torch.float32: _lib.VR_F32, torch.uint8: _lib.VR_U8, torch.int16: _lib.VR_I16,
+                 torch.float16: _lib.VR_F16}
+        if hasattr(torch, "uint16"):
+            codes[torch.uint16] = _lib.VR_U16
+        if t.dtype not in codes or not t.is_cuda or not t.is_contiguous():
+            raise TypeError("DeviceVolume needs a contiguous float32, uint8, uint16, int16 or float16 cuda tensor")
+        code = codes[t.dtype]
+        if unorm:
+            if code not in (_lib.VR_U8, _lib.VR_U16):
+                raise TypeError("unorm is for uint8 / uint16 tensors only")
+            code |= _lib.VR_DTYPE_UNORM
         dims = dims if dims is not None else tuple(reversed(t.shape))  # C-order (z,y,x) tensor -> (x,y,z)
-        return cls(t.data_ptr(), dims, last_update, owner=t)
+        return cls(t.data_ptr(), dims, last_update, owner=t, dtype=code)
 
     def min(self):
         return 0.0
@@ -94,11 +138,20 @@ def _vr_volume(vol) -> VrVolume:
             v.dims[i] = vol.dims[i]
         v.last_update = int(vol.TimeLastUpdate)
         v.location = _lib.VR_DEVICE
+        v.dtype = vol.dtype
         return v
     data = vol.Data
-    if not (isinstance(data, np.ndarray) and data.dtype == np.float32 and
+    raw = getattr(vol, "RawData", None)  # a RawVolume: its native-typed array instead of Data
+    unorm = False
+    if raw is not None and getattr(raw, "size", 0):
+        data = raw
+        unorm = bool(getattr(vol, "Unorm", False))
+    if not (isinstance(data, np.ndarray) and data.dtype in _NP_DTYPES and
             (data.flags.f_contiguous or data.ndim <= 1)):
-        raise TypeError("Volume.Data must be a column-major single array")
+        raise TypeError("Volume.Data must be a column-major single (or uint8, uint16, int16, float16) array")
+    if unorm and data.dtype not in (np.uint8, np.uint16):
+        raise TypeError("Unorm is for uint8 / uint16 data only")
+    v.dtype = dtype_code(data.dtype, unorm)
     v.data = data.ctypes.data if data.size else None
     d = _matlab_dims(data)
     for i in range(3):
@@ -138,7 +191,7 @@ def render_args(lights_arg, illum_arg, factors, element_size_um, resolution, rot
                 arr[i].position[k] = pos[k]
                 arr[i].color[k] = col[k]
         illum = _vr_volume(illum_arg)
-        keep += [arr, illum, getattr(illum_arg, "Data", None)]
+        keep += [arr, illum, getattr(illum_arg, "Data", None), getattr(illum_arg, "RawData", None)]
         ra.lights = ctypes.cast(arr, ctypes.POINTER(VrLight))
         ra.num_lights = len(lights)
         ra.illumination = ctypes.pointer(illum)
@@ -324,7 +377,7 @@ def channel(handle, t_sync, volumes, render_argv):
         c.dx, c.dy, c.dz = (ctypes.pointer(v) for v in vols[3:])
     ra, keep = render_args(*render_argv)
     c.args = ctypes.pointer(ra)
-    return c, [vols, ra, keep, [getattr(v, "Data", None) for v in volumes]]
+    return c, [vols, ra, keep, [(getattr(v, "Data", None), getattr(v, "RawData", None)) for v in volumes]]
 
 
 def render_channels(channels, stereo: bool = False, base: float = 0.0):
