@@ -222,6 +222,46 @@ int vr_sum_channels_device(const float *d_in, int32_t n, int32_t views, uint64_t
 int vr_render_device(vr_context *h, const vr_render_args *args, const vr_partition *part,
                      float *d_out, unsigned long long *d_steps, void *stream);
 
+/* --- projections through the current camera (no reference counterpart) ------------------------
+ * A projection marches exactly the ray of 'render': the same pixel-to-ray mapping and box
+ * intersection, tnear clamped to 0, the same tstep, the recurrences t += tstep and pos += step and
+ * the same max_steps cap.  It has no early exit on opacity: the loop ends only when t > tfar or on
+ * the cap, so every ray takes the samples k = 0 .. n-1 that 'render' would take with an opacity
+ * threshold that is never reached.  v_k is the trilinear sample of the EMISSION texture at sample k,
+ * fetched through the slot index as 'render' does (an unbound texture gives 0, a 1x1x1 texture its
+ * voxel through the same lerp algebra).  Ignored in vr_render_args: the lights and the illumination
+ * LUT (not uploaded; the handle's light state is left as it is), factors[1], factors[2] and
+ * opacity_threshold.  props[0] (the camera x offset) is honoured.  With Fe = factors[0]:
+ *   VR_PROJ_MIP  m = -inf, no winner; for k = 0 .. n-1: if v_k > m then m = v_k, t* = the march's t
+ *                at sample k (strictly greater: the first sample that attains the maximum wins; a
+ *                NaN sample never wins).  pixel = (Fe * (m + 0.0f)) * color[c] (the + 0.0f turns -0
+ *                into +0); aux = t*, the distance from the eye in the march's units, exactly the
+ *                value of the t recurrence.  A ray that misses the box, or one with no winning
+ *                sample (every sample NaN or -inf): pixel 0, aux NaN.
+ *   VR_PROJ_SUM  s = 0; s = s + v_k in sample order, one fp32 addition per sample.
+ *                pixel = ((Fe * s) * tstep) * color[c]; aux = (float)n (the mean projection is
+ *                pixel / (n * tstep)).  A miss: pixel 0, aux 0.  NaN and inf propagate.
+ * The image is laid out as 'render' writes it: [H, W, 3] column-major, or for a part the
+ * plane_cols stride documented at vr_partition; the aux plane is [H, W], resp. [max_cols][H].
+ * Empty space is leaped through the emission texture's occupancy map where it has one (both planes
+ * bit-identical to the march without; VR_PROJ_NO_PROBE=1, a test switch, turns the leap off).
+ * The mode is checked first (unknown: VR_ERR_ARGUMENT, before the handle: needs no device); a
+ * multi-device group handle is VR_ERR_UNSUPPORTED; a NULL out / d_out with a non-empty image is
+ * VR_ERR_ARGUMENT.  A degenerate frame (no emission volume synced) writes zeros, and the miss
+ * values to aux. */
+enum vr_projection { VR_PROJ_MIP = 0, VR_PROJ_SUM = 1 };
+
+/* Into the caller-owned host image out[H*W*3] and, if not NULL, out_aux[H*W]. */
+int vr_render_projection(vr_context *h, const vr_render_args *args, int32_t mode, float *out,
+                         float *out_aux /* may be NULL */);
+
+/* Into device memory on `stream` (asynchronous, as vr_render_device), the whole image or a part.
+ * d_steps, if not NULL, points to at least two counters: d_steps[0] += samples visited, leaped
+ * ones included (the sum of n over the rays); d_steps[1] += samples actually fetched. */
+int vr_render_projection_device(vr_context *h, const vr_render_args *args, int32_t mode,
+                                const vr_partition *part, float *d_out, float *d_aux /* may be NULL */,
+                                unsigned long long *d_steps /* may be NULL */, void *stream);
+
 /* Number of columns a part owns for image width w. */
 int64_t vr_partition_columns(int64_t w, const vr_partition *part);
 

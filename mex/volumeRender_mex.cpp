@@ -242,5 +242,27 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     if (nlhs > 1) plhs[1] = right; else mxDestroyArray(right);
     return;
   }
+  if (!strcmp(cmd, "render_projection")) {
+    // volumeRender('render_projection', h, <render args>, mode) -> [img, aux] (vr_render_projection):
+    // mode 'mip' -- the maximum of the emission volume along each ray, aux the depth of the first
+    // maximum (NaN: no volume hit) -- or 'sum' -- the ray sum, aux the ray's sample count
+    if (nlhs > 2) mexErrMsgTxt("Too many output arguments.");
+    if (nrhs < 12) mexErrMsgTxt("insufficient parameter!");
+    char mode[16];
+    if (mxGetString(prhs[11], mode, sizeof(mode))) mexErrMsgTxt("render_projection: mode must be 'mip' or 'sum'");
+    int32_t m = VR_PROJ_MIP;
+    if (!strcmp(mode, "sum")) m = VR_PROJ_SUM;
+    else if (strcmp(mode, "mip")) mexErrMsgTxt("render_projection: mode must be 'mip' or 'sum'");
+    vr_render_args a;
+    std::vector<vr_light> lights;
+    vr_volume illum{};
+    unpack_render(prhs + 2, a, lights, illum);
+    mxArray *img = new_image(a, 1);
+    mxArray *aux = mxCreateNumericMatrix((mwSize)a.resolution[0], (mwSize)a.resolution[1], mxSINGLE_CLASS, mxREAL);
+    check(vr_render_projection(h, &a, m, static_cast<float *>(mxGetData(img)), static_cast<float *>(mxGetData(aux))));
+    plhs[0] = img;
+    if (nlhs > 1) plhs[1] = aux; else mxDestroyArray(aux);
+    return;
+  }
   mexErrMsgTxt(("Unknown command: " + std::string(cmd)).c_str());
 }

@@ -19,6 +19,8 @@ VR_DEVICE = 1
 # enum vr_dtype (include/vrhip.h): element type of VrVolume.data; VR_DTYPE_UNORM ORed onto U8 / U16
 VR_F32, VR_U8, VR_U16, VR_I16, VR_F16 = 0, 1, 2, 3, 4
 VR_DTYPE_UNORM = 0x100
+# enum vr_projection
+VR_PROJ_MIP, VR_PROJ_SUM = 0, 1
 
 
 class VrVolume(ctypes.Structure):
@@ -86,6 +88,9 @@ SIGNATURES = [
                                  c_void_p]),
     ("vr_render_stereo_device", c_int, [c_void_p, POINTER(VrRenderArgs), c_float, c_void_p, c_void_p, c_void_p,
                                         c_void_p]),
+    ("vr_render_projection", c_int, [c_void_p, POINTER(VrRenderArgs), c_int32, c_void_p, c_void_p]),
+    ("vr_render_projection_device", c_int, [c_void_p, POINTER(VrRenderArgs), c_int32, POINTER(VrPartition), c_void_p,
+                                            c_void_p, c_void_p, c_void_p]),
     ("vr_partition_columns", c_int64, [c_int64, POINTER(VrPartition)]),
     ("vr_assemble_partitions", c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int64, c_void_p,
                                        c_void_p]),

@@ -48,6 +48,8 @@ int exact_lanes(int K, bool fast) { return (fast || VR_WITH_K8) ? K : std::min(K
 
 namespace vr {
 hipError_t launch_render(const RenderParams &P, int mode, bool ab_alias, bool big, bool share, hipStream_t s);
+// vr_project.hip: mode = vr_projection; aux: the [plane_cols][H] aux plane or null
+hipError_t launch_project(const RenderParams &P, int mode, float *aux, bool big, bool probe, hipStream_t s);
 // vr_march.hip built with VR_MARCH_FAST=1 / 0 (namespaces fast / exact) and VR_MARCH_K = 1, 2, 4, 8
 #define VR_DECL_MARCH(ns)                                                                                 \
   namespace ns {                                                                                         \
@@ -1579,6 +1581,47 @@ int do_render(vr_context *h, const vr_render_args *a, const vr_partition *part, 
   return VR_OK;
 }
 
+// Projection render (vr_render_projection, vr_project.hip): the frame geometry, the probe margin and
+// the occupancy pointers of build_frame and the partition fields of do_render; no lights are
+// uploaded or staged, and nothing of the texture unit, the slot indices or the march's schedules is
+// written -- a render before and after a projection gives the same bits.
+int do_project(vr_context *h, const vr_render_args *a, int32_t mode, const vr_partition *part, float *d_out,
+               float *d_aux, unsigned long long *d_steps, hipStream_t stream) {
+  Frame F;
+  int rc = build_frame(h, a, F);
+  if (rc) return rc;
+  rc = validate_partition(part);
+  if (rc) return rc;
+  vr::RenderParams &P = F.P;
+  P.block_cols = part ? part->block_cols : std::max<int32_t>(P.width, 1);
+  P.part = part ? part->part : 0;
+  P.num_parts = part ? part->num_parts : 1;
+  P.part_cols = (int32_t)part_columns(P.width, P.block_cols, P.part, P.num_parts);
+  P.plane_cols = (int32_t)part_columns(P.width, P.block_cols, 0, P.num_parts);
+  P.out = d_out;
+  P.steps = d_steps;
+  P.tile_mode = 0;
+  P.views = 1;
+  const size_t plane = (size_t)P.plane_cols * (size_t)P.height;
+  if (plane && !d_out) return fail(VR_ERR_ARGUMENT, "output is NULL");
+  if (F.degenerate) {  // no synced emission volume: render's zeros, and every ray a miss
+    if (plane) VR_HIP(hipMemsetAsync(d_out, 0, plane * 3 * sizeof(float), stream));
+    if (plane && d_aux)
+      VR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_aux), mode == VR_PROJ_MIP ? 0x7fc00000 : 0, plane,
+                               stream));
+    return VR_OK;
+  }
+  // VR_PROJ_NO_PROBE=1 (test switch): every sample fetched, no empty-space leap
+  const bool probe = P.occ != nullptr && !test_flag("VR_PROJ_NO_PROBE");
+  LaunchRec L;
+  L.stream = stream;
+  L.device = h->device;
+  bind_reads(L);
+  VR_HIP(vr::launch_project(P, mode, d_aux, F.big, probe, stream));
+  VR_HIP(L.finish());
+  return VR_OK;
+}
+
 // Sort-last slab render: the handle's emission volume holds planes
 // [z_first, z_first + d2) of a volume of depth `depth`; the frame is built for the whole volume
 // (box, step, gradient offsets) and the march takes the samples of [z0, z1) only.
@@ -2616,6 +2659,49 @@ int vr_render_device(vr_context *h, const vr_render_args *a, const vr_partition 
   if (!h->children.empty() && !part && !d_steps) return group_render(h, a, d_out, (hipStream_t)stream);
   Frame F;
   return do_render(h, a, part, d_out, d_steps, (hipStream_t)stream, F);
+  VR_GUARD_END
+}
+
+int vr_render_projection_device(vr_context *h, const vr_render_args *a, int32_t mode, const vr_partition *part,
+                                float *d_out, float *d_aux, unsigned long long *d_steps, void *stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (mode != VR_PROJ_MIP && mode != VR_PROJ_SUM) return fail(VR_ERR_ARGUMENT, "unknown projection mode");
+  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
+  if (!a) return fail(VR_ERR_ARGUMENT, "insufficient parameter!");
+  if (!h->children.empty()) return fail(VR_ERR_UNSUPPORTED, "vr_render_projection_device: one-device handles only");
+  VR_GUARD_BEGIN
+  DeviceGuard dg(h->device);
+  vr_host::prune_retired();
+  return do_project(h, a, mode, part, d_out, d_aux, d_steps, (hipStream_t)stream);
+  VR_GUARD_END
+}
+
+int vr_render_projection(vr_context *h, const vr_render_args *a, int32_t mode, float *out, float *out_aux) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (mode != VR_PROJ_MIP && mode != VR_PROJ_SUM) return fail(VR_ERR_ARGUMENT, "unknown projection mode");
+  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
+  if (!a) return fail(VR_ERR_ARGUMENT, "insufficient parameter!");
+  if (!h->children.empty()) return fail(VR_ERR_UNSUPPORTED, "vr_render_projection: one-device handles only");
+  VR_GUARD_BEGIN
+  DeviceGuard dg(h->device);
+  vr_host::prune_retired();
+  // the image and, behind it, the aux plane in the handle's output buffer
+  const size_t plane = (size_t)a->resolution[0] * (size_t)a->resolution[1] * sizeof(float);
+  const size_t bytes = 4 * plane;
+  if (plane && !out) return fail(VR_ERR_ARGUMENT, "output is NULL");
+  if (bytes > h->d_out_bytes) {
+    if (h->d_out) VR_HIP(hipFree(h->d_out));
+    h->d_out = nullptr;
+    h->d_out_bytes = 0;
+    VR_HIP(hipMalloc(&h->d_out, bytes));
+    h->d_out_bytes = bytes;
+  }
+  float *d_aux = out_aux ? h->d_out + 3 * (plane / sizeof(float)) : nullptr;
+  const int rc = do_project(h, a, mode, nullptr, h->d_out, d_aux, nullptr, nullptr);
+  if (rc) return rc;
+  if (plane) VR_HIP(hipMemcpy(out, h->d_out, 3 * plane, hipMemcpyDeviceToHost));
+  if (plane && out_aux) VR_HIP(hipMemcpy(out_aux, d_aux, plane, hipMemcpyDeviceToHost));
+  return VR_OK;
   VR_GUARD_END
 }
 

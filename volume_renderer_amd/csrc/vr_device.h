@@ -138,12 +138,15 @@ struct RenderParams {
   uint32_t pre_cap;
 };
 
-// The views of one multi-view launch (vr_render_channels), passed by value: 4 x 832 B of kernel
-// arguments.
+// The views of one multi-view launch (vr_render_channels), passed by value: 4 x 1040 B = 4160 B of
+// kernel arguments.  That is already past 4 KiB (the limit CUDA documents; the launches here run
+// with it), so RenderParams does not grow: a kernel that needs more takes a second small struct
+// (vr_project.hip ProjectExtras).  The assertion pins today's size; shrink the struct before adding.
 #define VR_VIEWS_MAX 4
 struct RenderViews {
   RenderParams p[VR_VIEWS_MAX];
 };
+static_assert(sizeof(RenderViews) <= 4160, "RenderParams grew: RenderViews passes four by value as kernel arguments");
 
 // Per-buffer statistics computed on the device at upload (used to prove the empty-sample skip
 // exact): any non-finite voxel, and the largest magnitude.

@@ -285,6 +285,31 @@ def render_stereo_device(handle, ra: VrRenderArgs, base: float, d_left: int, d_r
                                         ctypes.c_void_p(int(stream)) if stream else None))
 
 
+PROJECTION_MODES = {"mip": _lib.VR_PROJ_MIP, "sum": _lib.VR_PROJ_SUM}
+
+
+def projection_mode(mode) -> int:
+    """The vr_projection code of 'mip' / 'sum' (or of a code itself)."""
+    if isinstance(mode, str):
+        if mode.lower() not in PROJECTION_MODES:
+            raise _lib.VrError(1, "unknown projection mode")
+        return PROJECTION_MODES[mode.lower()]
+    return int(mode)
+
+
+def render_projection_device(handle, ra: VrRenderArgs, mode, d_out: int, d_aux: int = 0, part=None, d_steps: int = 0,
+                             stream: int = 0) -> None:
+    """A projection into device memory (vr_render_projection_device), asynchronous on `stream`:
+    mode 'mip' (aux: the depth t of the first maximum) or 'sum' (aux: the ray's sample count);
+    d_aux = 0: no aux plane; d_steps: two counters, samples visited and samples fetched."""
+    check(lib().vr_render_projection_device(_handle(handle), ctypes.byref(ra), projection_mode(mode),
+                                            ctypes.byref(part) if part is not None else None,
+                                            ctypes.c_void_p(int(d_out)) if d_out else None,
+                                            ctypes.c_void_p(int(d_aux)) if d_aux else None,
+                                            ctypes.c_void_p(int(d_steps)) if d_steps else None,
+                                            ctypes.c_void_p(int(stream)) if stream else None))
+
+
 def set_option(name: str, value: int) -> None:
     """vr_set_option: a process-wide library option (include/vrhip.h)."""
     check(lib().vr_set_option(name.encode(), int(value)))
@@ -420,7 +445,8 @@ def _group_devices():
 
 
 def volumeRender(cmd, *args):
-    """The `volumeRender` mex: commands 'new', 'delete', 'mem_info', 'sync_volumes', 'render'."""
+    """The `volumeRender` mex: commands 'new', 'delete', 'mem_info', 'sync_volumes', 'render' (and
+    'render_stereo', 'render_channels', 'render_projection', which the reference does not have)."""
     nrhs = 1 + len(args)
     if not isinstance(cmd, str) or len(cmd) >= 64:
         raise _lib.VrError(1, "First input should be a command string less than 64 characters long.")
@@ -479,6 +505,19 @@ def volumeRender(cmd, *args):
                                  right.ctypes.data_as(ctypes.c_void_p) if right.size else None))
         del keep
         return left, right
+    if cmd == "render_projection":  # ('render_projection', h, <the nine render arguments>, mode)
+        if nrhs < 12:
+            raise _lib.VrError(1, "insufficient parameter!")
+        ra, keep = render_args(*args[1:10])
+        res = np.asarray(args[5]).reshape(-1)
+        H, W = int(res[0]), int(res[1])
+        out = np.zeros((H, W, 3), dtype=np.float32, order="F")
+        aux = np.zeros((H, W), dtype=np.float32, order="F")
+        check(L.vr_render_projection(h, ctypes.byref(ra), projection_mode(args[10]),
+                                     out.ctypes.data_as(ctypes.c_void_p) if out.size else None,
+                                     aux.ctypes.data_as(ctypes.c_void_p) if aux.size else None))
+        del keep
+        return out, aux
     if cmd == "render":
         if nrhs < 11:
             raise _lib.VrError(1, "insufficient parameter!")

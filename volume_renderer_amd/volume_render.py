@@ -178,6 +178,31 @@ class VolumeRender:
             left = self._p_render(-base, resolution)
         return self._compose(left, right, delta)
 
+    def renderProjection(self, mode="mip", aux=False):
+        """A projection through the current camera (vr_render_projection): mode 'mip', the maximum
+        of the emission volume along each ray, or 'sum', the ray sum (times FactorEmission, Color and,
+        for the sum, the step length).  aux=True also returns the [H, W] aux plane: for 'mip' the
+        distance from the eye to the first maximum (NaN where the ray misses the volume), for 'sum'
+        the ray's sample count.  With CameraXOffset ~= 0 the two eyes are projected and composed as
+        render() composes them; a stereo projection has no aux plane."""
+        res = np.flip(self.ImageResolution)  # [H W]
+        if self.CameraXOffset == 0:
+            img, plane = self._p_project(np.float32(self.CameraXOffset), res, mode)
+            return (img, plane) if aux else img
+        if aux:
+            raise ValueError("a stereo projection returns no aux plane")
+        base, delta, resolution = self._stereo_geometry()
+        right = self._p_project(base, resolution, mode)[0]
+        left = self._p_project(-base, resolution, mode)[0]
+        return self._compose(left, right, delta)
+
+    def _p_project(self, camera_x_offset, resolution, mode):
+        """Validate and sync the volumes as _p_render does, then 'render_projection'."""
+        self._validate_volumes()
+        self.syncVolumes()
+        return volumeRender("render_projection", self.objectHandle, *self._render_argv(camera_x_offset, resolution),
+                            mode)
+
     def _fused_stereo(self) -> bool:
         """Both eyes in one launch (vr_render_stereo), the default since round 6: on one GPU the
         fused launch, scheduled over both views' blocks, measured 82.05 vs 84.01 ms for the
