@@ -262,6 +262,55 @@ int vr_render_projection_device(vr_context *h, const vr_render_args *args, int32
                                 const vr_partition *part, float *d_out, float *d_aux /* may be NULL */,
                                 unsigned long long *d_steps /* may be NULL */, void *stream);
 
+/* --- first-hit isosurface through the current camera (no reference counterpart) ---------------
+ * The opaque surface v = level of the EMISSION texture, lit by the scene's lights, with its depth and
+ * normal planes.
+ * Search.  The ray is exactly that of 'render' and of the projections: the same pixel-to-ray mapping
+ * and box intersection, tnear clamped to 0, tstep, the recurrences t += tstep and pos += step, and
+ * the max_steps cap; there is no opacity exit.  v_k is the trilinear emission sample at sample k,
+ * fetched through the slot index as the projections do (an unbound texture reads 0, a 1x1x1 texture
+ * gives its voxel through the lerp algebra).  The hit is the first k with v_k >= level; a NaN sample
+ * is never >=, in the search and in the refinement alike.  The ray stops at the hit.  No hit before
+ * t > tfar or before the cap: no surface.
+ * Refinement (VR_ISO_REFINE = 6 bisection steps, a compile-time constant).  k = 0: the surface point
+ * is the first sample itself, p* = pos_0, t* = t_0 (the box face cuts the object).  k > 0: lo = 0,
+ * hi = 1; six times c = (lo + hi) * 0.5f, q_i = fmaf(step_i, c, pos_{k-1,i}), v = the emission sample
+ * at (q - bmin) * bscale, v >= level ? hi = c : lo = c; then p*_i = fmaf(step_i, hi, pos_{k-1,i}) and
+ * t* = fmaf(tstep, hi, t_{k-1}) (hi = 1 gives pos_k and t_k bit for bit).  v* is the emission sample
+ * at p*.
+ * Surface sample.  g is the gradient 'render''s exact shading takes at a sample at p*, by the handle's
+ * gradient method whether or not there are lights: on the fly, the six taps at
+ * ((pos +- gstep) - bmin) * bscale of the emission binding, times 0.5 (never the half-texel fast
+ * taps); lookup, the three gradient textures at p*.  n = -(g * (1 / sqrtf(dot(g, g)))); a zero
+ * gradient gives NaN, as in 'render'.  ill is 'render''s exact (oracle-order) shading at p* with
+ * refl = Fr * reflection(p*); the lights and the illumination LUT are uploaded and checked exactly as
+ * 'render' does (a typed LUT: VR_ERR_UNSUPPORTED) and stay the handle's light state; without lights
+ * or without a LUT ill = 0.  pixel_c = fmaf(Fe * v*, color[c], ill_c).  opacity_threshold and
+ * factors[2] are ignored; props[0] is honoured.
+ * Outputs.  The image is laid out as 'render' writes it, whole or as a part; the depth plane, t*, as
+ * the projections' aux plane ([H, W], resp. [max_cols][H]); the normal plane, n.x, n.y, n.z, in three
+ * planes laid out like the image.  A pixel without a surface (the ray misses the box, or no sample
+ * hits): image 0, depth NaN, normal NaN; a degenerate frame (no emission volume synced) writes those
+ * everywhere.  Empty space is leaped through the emission texture's occupancy map when level > 0 (a
+ * leaped run's samples are +-0 and cannot hit; every plane bit-identical to the march without;
+ * VR_ISO_NO_PROBE=1, a test switch, turns the leap off).
+ * A NaN level is VR_ERR_ARGUMENT, checked before the handle (needs no device); +-inf is allowed.  A
+ * multi-device group handle is VR_ERR_UNSUPPORTED; a NULL out / d_out with a non-empty image is
+ * VR_ERR_ARGUMENT.  The call changes only what 'render' changes, the handle's light and LUT state: a
+ * 'render' before and after gives the same bits. */
+#define VR_ISO_REFINE 6
+
+/* Into the caller-owned host image out[H*W*3] and, where not NULL, out_depth[H*W], out_normal[H*W*3]. */
+int vr_render_isosurface(vr_context *h, const vr_render_args *args, float level, float *out,
+                         float *out_depth /* [H,W], may be NULL */, float *out_normal /* [H,W,3], may be NULL */);
+
+/* Into device memory on `stream` (asynchronous, as vr_render_device), the whole image or a part.
+ * d_steps, if not NULL, points to at least three counters: d_steps[0] += search samples visited,
+ * leaped ones included; d_steps[1] += search samples fetched; d_steps[2] += surface pixels. */
+int vr_render_isosurface_device(vr_context *h, const vr_render_args *args, float level, const vr_partition *part,
+                                float *d_out, float *d_depth, float *d_normal,
+                                unsigned long long *d_steps /* 3 counters, may be NULL */, void *stream);
+
 /* Number of columns a part owns for image width w. */
 int64_t vr_partition_columns(int64_t w, const vr_partition *part);
 

@@ -264,5 +264,31 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     if (nlhs > 1) plhs[1] = aux; else mxDestroyArray(aux);
     return;
   }
+  if (!strcmp(cmd, "render_isosurface")) {
+    // volumeRender('render_isosurface', h, <render args>, level) -> [img, depth, normal]
+    // (vr_render_isosurface): the first-hit surface emission == level lit by the lights, the depth of
+    // the surface point [H W] and its unit normal [H W 3] (NaN where there is no surface)
+    if (nlhs > 3) mexErrMsgTxt("Too many output arguments.");
+    if (nrhs < 12) mexErrMsgTxt("insufficient parameter!");
+    const mxClassID lc = mxGetClassID(prhs[11]);
+    const bool numeric = lc == mxDOUBLE_CLASS || lc == mxSINGLE_CLASS || lc == mxINT8_CLASS || lc == mxUINT8_CLASS ||
+                         lc == mxINT16_CLASS || lc == mxUINT16_CLASS || lc == mxINT32_CLASS || lc == mxUINT32_CLASS ||
+                         lc == mxINT64_CLASS || lc == mxUINT64_CLASS;
+    if (!numeric || mxIsComplex(prhs[11]) || mxGetNumberOfElements(prhs[11]) != 1)
+      mexErrMsgTxt("render_isosurface: level must be a real scalar");
+    const float level = (float)mxGetScalar(prhs[11]);
+    vr_render_args a;
+    std::vector<vr_light> lights;
+    vr_volume illum{};
+    unpack_render(prhs + 2, a, lights, illum);
+    mxArray *img = new_image(a, 1), *normal = new_image(a, 1);
+    mxArray *depth = mxCreateNumericMatrix((mwSize)a.resolution[0], (mwSize)a.resolution[1], mxSINGLE_CLASS, mxREAL);
+    check(vr_render_isosurface(h, &a, level, static_cast<float *>(mxGetData(img)),
+                               static_cast<float *>(mxGetData(depth)), static_cast<float *>(mxGetData(normal))));
+    plhs[0] = img;
+    if (nlhs > 1) plhs[1] = depth; else mxDestroyArray(depth);
+    if (nlhs > 2) plhs[2] = normal; else mxDestroyArray(normal);
+    return;
+  }
   mexErrMsgTxt(("Unknown command: " + std::string(cmd)).c_str());
 }

@@ -91,6 +91,9 @@ SIGNATURES = [
     ("vr_render_projection", c_int, [c_void_p, POINTER(VrRenderArgs), c_int32, c_void_p, c_void_p]),
     ("vr_render_projection_device", c_int, [c_void_p, POINTER(VrRenderArgs), c_int32, POINTER(VrPartition), c_void_p,
                                             c_void_p, c_void_p, c_void_p]),
+    ("vr_render_isosurface", c_int, [c_void_p, POINTER(VrRenderArgs), c_float, c_void_p, c_void_p, c_void_p]),
+    ("vr_render_isosurface_device", c_int, [c_void_p, POINTER(VrRenderArgs), c_float, POINTER(VrPartition), c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p]),
     ("vr_partition_columns", c_int64, [c_int64, POINTER(VrPartition)]),
     ("vr_assemble_partitions", c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int64, c_void_p,
                                        c_void_p]),

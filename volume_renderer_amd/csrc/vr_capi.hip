@@ -50,6 +50,8 @@ namespace vr {
 hipError_t launch_render(const RenderParams &P, int mode, bool ab_alias, bool big, bool share, hipStream_t s);
 // vr_project.hip: mode = vr_projection; aux: the [plane_cols][H] aux plane or null
 hipError_t launch_project(const RenderParams &P, int mode, float *aux, bool big, bool probe, hipStream_t s);
+hipError_t launch_isosurface(const RenderParams &P, int grad, float level, float *depth, float *normal, bool big,
+                             bool probe, hipStream_t s);
 // vr_march.hip built with VR_MARCH_FAST=1 / 0 (namespaces fast / exact) and VR_MARCH_K = 1, 2, 4, 8
 #define VR_DECL_MARCH(ns)                                                                                 \
   namespace ns {                                                                                         \
@@ -1622,6 +1624,63 @@ int do_project(vr_context *h, const vr_render_args *a, int32_t mode, const vr_pa
   return VR_OK;
 }
 
+// Isosurface render (vr_render_isosurface, vr_isosurface.hip): the lights and the LUT uploaded and
+// checked as do_render does, the frame geometry, the probe margin and the occupancy pointers of
+// build_frame, the partition fields of do_project.  The gradient method is the handle's whether or
+// not there are lights (the normal plane needs it).  Only the handle's light and LUT state is
+// written, as by a render: nothing of the texture unit, the slot indices or the march's schedules.
+int do_isosurface(vr_context *h, const vr_render_args *a, float level, const vr_partition *part, float *d_out,
+                  float *d_depth, float *d_normal, unsigned long long *d_steps, hipStream_t stream) {
+  if (a->num_lights > 0 && !a->lights) return fail(VR_ERR_ARGUMENT, "lights is NULL");
+  if (a->num_lights >= 0)
+    if (int rc = check_dtype(a->illumination, true, "illumination volume")) return rc;
+  if (a->num_lights >= 0 && a->illumination) {
+    const uint64_t required = required_memory(h) +
+                              a->illumination->dims[0] * a->illumination->dims[1] * a->illumination->dims[2] * 4 +
+                              (uint64_t)a->num_lights * sizeof(vr::DevLight);
+    if (int rc = check_free_device_memory(required)) return rc;
+  }
+  upload_lights(h, a);
+  Frame F;
+  int rc = build_frame(h, a, F);
+  if (rc) return rc;
+  rc = validate_partition(part);
+  if (rc) return rc;
+  vr::RenderParams &P = F.P;
+  P.block_cols = part ? part->block_cols : std::max<int32_t>(P.width, 1);
+  P.part = part ? part->part : 0;
+  P.num_parts = part ? part->num_parts : 1;
+  P.part_cols = (int32_t)part_columns(P.width, P.block_cols, P.part, P.num_parts);
+  P.plane_cols = (int32_t)part_columns(P.width, P.block_cols, 0, P.num_parts);
+  P.out = d_out;
+  P.steps = d_steps;
+  P.tile_mode = 0;
+  P.views = 1;
+  P.fast_shade = 0;
+  if (P.lut.p == nullptr) P.num_lights = 0;  // no LUT: no illumination term
+  const size_t plane = (size_t)P.plane_cols * (size_t)P.height;
+  if (plane && !d_out) return fail(VR_ERR_ARGUMENT, "output is NULL");
+  if (F.degenerate) {  // no synced emission volume: no surface anywhere
+    if (plane) VR_HIP(hipMemsetAsync(d_out, 0, plane * 3 * sizeof(float), stream));
+    if (plane && d_depth)
+      VR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_depth), 0x7fc00000, plane, stream));
+    if (plane && d_normal)
+      VR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_normal), 0x7fc00000, plane * 3, stream));
+    return VR_OK;
+  }
+  // VR_ISO_NO_PROBE=1 (test switch): every sample fetched, no empty-space leap
+  const bool probe = P.occ != nullptr && level > 0.f && !test_flag("VR_ISO_NO_PROBE");
+  LaunchRec L;
+  L.stream = stream;
+  L.device = h->device;
+  bind_reads(L);
+  stage_frame(L, P, g_tex.lights);
+  VR_HIP(vr::launch_isosurface(P, g_tex.grad_method == G_LOOKUP ? 2 : 1, level, d_depth, d_normal, F.big, probe,
+                               stream));
+  VR_HIP(L.finish());
+  return VR_OK;
+}
+
 // Sort-last slab render: the handle's emission volume holds planes
 // [z_first, z_first + d2) of a volume of depth `depth`; the frame is built for the whole volume
 // (box, step, gradient offsets) and the march takes the samples of [z0, z1) only.
@@ -2701,6 +2760,53 @@ int vr_render_projection(vr_context *h, const vr_render_args *a, int32_t mode, f
   if (rc) return rc;
   if (plane) VR_HIP(hipMemcpy(out, h->d_out, 3 * plane, hipMemcpyDeviceToHost));
   if (plane && out_aux) VR_HIP(hipMemcpy(out_aux, d_aux, plane, hipMemcpyDeviceToHost));
+  return VR_OK;
+  VR_GUARD_END
+}
+
+int vr_render_isosurface_device(vr_context *h, const vr_render_args *a, float level, const vr_partition *part,
+                                float *d_out, float *d_depth, float *d_normal, unsigned long long *d_steps,
+                                void *stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (level != level) return fail(VR_ERR_ARGUMENT, "isosurface level is NaN");
+  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
+  if (!a) return fail(VR_ERR_ARGUMENT, "insufficient parameter!");
+  if (!h->children.empty()) return fail(VR_ERR_UNSUPPORTED, "vr_render_isosurface_device: one-device handles only");
+  VR_GUARD_BEGIN
+  DeviceGuard dg(h->device);
+  vr_host::prune_retired();
+  return do_isosurface(h, a, level, part, d_out, d_depth, d_normal, d_steps, (hipStream_t)stream);
+  VR_GUARD_END
+}
+
+int vr_render_isosurface(vr_context *h, const vr_render_args *a, float level, float *out, float *out_depth,
+                         float *out_normal) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (level != level) return fail(VR_ERR_ARGUMENT, "isosurface level is NaN");
+  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
+  if (!a) return fail(VR_ERR_ARGUMENT, "insufficient parameter!");
+  if (!h->children.empty()) return fail(VR_ERR_UNSUPPORTED, "vr_render_isosurface: one-device handles only");
+  VR_GUARD_BEGIN
+  DeviceGuard dg(h->device);
+  vr_host::prune_retired();
+  // the image and, behind it, the depth plane and the three normal planes in the handle's output buffer
+  const size_t plane = (size_t)a->resolution[0] * (size_t)a->resolution[1] * sizeof(float);
+  const size_t bytes = 7 * plane;
+  if (plane && !out) return fail(VR_ERR_ARGUMENT, "output is NULL");
+  if (bytes > h->d_out_bytes) {
+    if (h->d_out) VR_HIP(hipFree(h->d_out));
+    h->d_out = nullptr;
+    h->d_out_bytes = 0;
+    VR_HIP(hipMalloc(&h->d_out, bytes));
+    h->d_out_bytes = bytes;
+  }
+  float *d_depth = out_depth ? h->d_out + 3 * (plane / sizeof(float)) : nullptr;
+  float *d_normal = out_normal ? h->d_out + 4 * (plane / sizeof(float)) : nullptr;
+  const int rc = do_isosurface(h, a, level, nullptr, h->d_out, d_depth, d_normal, nullptr, nullptr);
+  if (rc) return rc;
+  if (plane) VR_HIP(hipMemcpy(out, h->d_out, 3 * plane, hipMemcpyDeviceToHost));
+  if (plane && out_depth) VR_HIP(hipMemcpy(out_depth, d_depth, plane, hipMemcpyDeviceToHost));
+  if (plane && out_normal) VR_HIP(hipMemcpy(out_normal, d_normal, 3 * plane, hipMemcpyDeviceToHost));
   return VR_OK;
   VR_GUARD_END
 }

@@ -310,6 +310,30 @@ def render_projection_device(handle, ra: VrRenderArgs, mode, d_out: int, d_aux: 
                                             ctypes.c_void_p(int(stream)) if stream else None))
 
 
+def isosurface_level(level) -> float:
+    """The level of an isosurface render: a real scalar."""
+    v = np.asarray(level)
+    if v.size != 1 or v.dtype.kind not in "fiu":
+        raise _lib.VrError(1, "render_isosurface: level must be a real scalar")
+    return float(v.reshape(-1)[0])
+
+
+def render_isosurface_device(handle, ra: VrRenderArgs, level, d_out: int, d_depth: int = 0, d_normal: int = 0,
+                             part=None, d_steps: int = 0, stream: int = 0) -> None:
+    """The first-hit isosurface emission == level into device memory (vr_render_isosurface_device),
+    asynchronous on `stream`: the lit image, the depth plane t* (d_depth = 0: none) and the three
+    normal planes (d_normal = 0: none); d_steps: three counters, search samples visited, search
+    samples fetched, surface pixels."""
+    lv = ctypes.c_float(isosurface_level(level))
+    check(lib().vr_render_isosurface_device(_handle(handle), ctypes.byref(ra), lv,
+                                            ctypes.byref(part) if part is not None else None,
+                                            ctypes.c_void_p(int(d_out)) if d_out else None,
+                                            ctypes.c_void_p(int(d_depth)) if d_depth else None,
+                                            ctypes.c_void_p(int(d_normal)) if d_normal else None,
+                                            ctypes.c_void_p(int(d_steps)) if d_steps else None,
+                                            ctypes.c_void_p(int(stream)) if stream else None))
+
+
 def set_option(name: str, value: int) -> None:
     """vr_set_option: a process-wide library option (include/vrhip.h)."""
     check(lib().vr_set_option(name.encode(), int(value)))
@@ -446,7 +470,8 @@ def _group_devices():
 
 def volumeRender(cmd, *args):
     """The `volumeRender` mex: commands 'new', 'delete', 'mem_info', 'sync_volumes', 'render' (and
-    'render_stereo', 'render_channels', 'render_projection', which the reference does not have)."""
+    'render_stereo', 'render_channels', 'render_projection', 'render_isosurface', which the reference
+    does not have)."""
     nrhs = 1 + len(args)
     if not isinstance(cmd, str) or len(cmd) >= 64:
         raise _lib.VrError(1, "First input should be a command string less than 64 characters long.")
@@ -518,6 +543,22 @@ def volumeRender(cmd, *args):
                                      aux.ctypes.data_as(ctypes.c_void_p) if aux.size else None))
         del keep
         return out, aux
+    if cmd == "render_isosurface":  # ('render_isosurface', h, <the nine render arguments>, level)
+        if nrhs < 12:
+            raise _lib.VrError(1, "insufficient parameter!")
+        level = isosurface_level(args[10])
+        ra, keep = render_args(*args[1:10])
+        res = np.asarray(args[5]).reshape(-1)
+        H, W = int(res[0]), int(res[1])
+        out = np.zeros((H, W, 3), dtype=np.float32, order="F")
+        depth = np.zeros((H, W), dtype=np.float32, order="F")
+        normal = np.zeros((H, W, 3), dtype=np.float32, order="F")
+        check(L.vr_render_isosurface(h, ctypes.byref(ra), ctypes.c_float(level),
+                                     out.ctypes.data_as(ctypes.c_void_p) if out.size else None,
+                                     depth.ctypes.data_as(ctypes.c_void_p) if depth.size else None,
+                                     normal.ctypes.data_as(ctypes.c_void_p) if normal.size else None))
+        del keep
+        return out, depth, normal
     if cmd == "render":
         if nrhs < 11:
             raise _lib.VrError(1, "insufficient parameter!")

@@ -203,6 +203,33 @@ class VolumeRender:
         return volumeRender("render_projection", self.objectHandle, *self._render_argv(camera_x_offset, resolution),
                             mode)
 
+    def renderIsosurface(self, level, aux=False):
+        """The first-hit isosurface VolumeEmission == level through the current camera
+        (vr_render_isosurface): the opaque surface lit by LightSources / VolumeIllumination plus
+        FactorEmission times the surface value, black where no ray sample reaches the level.
+        aux=True also returns the [H, W] depth plane (the distance from the eye to the surface, NaN
+        without one) and the [H, W, 3] unit normal (NaN without a surface or on a zero gradient).
+        With CameraXOffset ~= 0 the two eyes are rendered and composed as render() composes them; a
+        stereo isosurface has no aux planes."""
+        res = np.flip(self.ImageResolution)  # [H W]
+        if self.CameraXOffset == 0:
+            img, depth, normal = self._p_isosurface(np.float32(self.CameraXOffset), res, level)
+            return (img, depth, normal) if aux else img
+        if aux:
+            raise ValueError("a stereo isosurface returns no aux planes")
+        base, delta, resolution = self._stereo_geometry()
+        right = self._p_isosurface(base, resolution, level)[0]
+        left = self._p_isosurface(-base, resolution, level)[0]
+        return self._compose(left, right, delta)
+
+    def _p_isosurface(self, camera_x_offset, resolution, level):
+        """Validate and sync the volumes as _p_render does (the lights and the LUT travel in the
+        render arguments), then 'render_isosurface'."""
+        self._validate_volumes()
+        self.syncVolumes()
+        return volumeRender("render_isosurface", self.objectHandle, *self._render_argv(camera_x_offset, resolution),
+                            level)
+
     def _fused_stereo(self) -> bool:
         """Both eyes in one launch (vr_render_stereo), the default since round 6: on one GPU the
         fused launch, scheduled over both views' blocks, measured 82.05 vs 84.01 ms for the
