@@ -882,7 +882,10 @@ int build_frame(vr_context *h, const vr_render_args *a, Frame &F, uint64_t depth
   }
   {
     const bool re_ok = P.re_is_em || (P.re.p && P.re.one);
-    const bool lut_ok = g_tex.lights.empty() || (P.lut.p && P.lut.small && !P.lut.one && P.lut.zp);
+    // (at most 8192 texels per LUT axis: the tame shading forms the LUT's filter weights with
+    // vr_sampling.h weight8_rn, which needs a texel coordinate below 2^14)
+    const bool lut_ok = g_tex.lights.empty() || (P.lut.p && P.lut.small && !P.lut.one && P.lut.zp &&
+                                                 std::max(P.lut.nx, std::max(P.lut.ny, P.lut.nz)) <= 8192);
     // (tstep > 0: the march's t only grows, which advance_k relies on)
     const bool step_ok = std::isfinite(P.tstep) && P.tstep > 0.f;
     P.tame = (P.skip_empty && P.eds_finite && P.small_x && re_ok && lut_ok && step_ok && !diag_flag("VR_NO_TAME")) ? 1

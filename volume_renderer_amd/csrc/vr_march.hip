@@ -443,7 +443,35 @@ __device__ __forceinline__ int group_max_i(int v, int acc) {
 template <int K, int I, bool ZF = false>
 __device__ __forceinline__ void composite_group(const RenderParams &P, Ray &R, float exf, float r, float gg, float b,
                                                 float alpha, float thr) {
-  if constexpr (I < K) {
+  if constexpr (K == 2 && ZF && I < K) {
+    // the tame two-lane group: sum = fma(1 - sum.a, sample I, sum) as v_fmac_f32 with the sample read
+    // through its DPP operand -- one slow-class instruction per sum where the move and the fma are a
+    // slow and a fast one (tools/microbench/valu_rates.hip).  The same fused multiply-add, in place.
+    // Both lanes of a pair are enabled together here (R.alive is the ray's), so the source lane is
+    // never a disabled one.  A DPP read of a VGPR that the preceding VALU instruction wrote owes two
+    // wait states, and the compiler does not look into the asm: the s_nop 1 pays them.
+    if (R.alive) {
+      const float om = 1.f - R.sa;
+      if constexpr (I == 0)
+        asm("s_nop 1\n\t"
+            "v_fmac_f32_dpp %0, %4, %8 quad_perm:[0,0,2,2] row_mask:0xf bank_mask:0xf\n\t"
+            "v_fmac_f32_dpp %1, %5, %8 quad_perm:[0,0,2,2] row_mask:0xf bank_mask:0xf\n\t"
+            "v_fmac_f32_dpp %2, %6, %8 quad_perm:[0,0,2,2] row_mask:0xf bank_mask:0xf\n\t"
+            "v_fmac_f32_dpp %3, %7, %8 quad_perm:[0,0,2,2] row_mask:0xf bank_mask:0xf"
+            : "+v"(R.sr), "+v"(R.sg), "+v"(R.sb), "+v"(R.sa)
+            : "v"(r), "v"(gg), "v"(b), "v"(alpha), "v"(om));
+      else
+        asm("s_nop 1\n\t"
+            "v_fmac_f32_dpp %0, %4, %8 quad_perm:[1,1,3,3] row_mask:0xf bank_mask:0xf\n\t"
+            "v_fmac_f32_dpp %1, %5, %8 quad_perm:[1,1,3,3] row_mask:0xf bank_mask:0xf\n\t"
+            "v_fmac_f32_dpp %2, %6, %8 quad_perm:[1,1,3,3] row_mask:0xf bank_mask:0xf\n\t"
+            "v_fmac_f32_dpp %3, %7, %8 quad_perm:[1,1,3,3] row_mask:0xf bank_mask:0xf"
+            : "+v"(R.sr), "+v"(R.sg), "+v"(R.sb), "+v"(R.sa)
+            : "v"(r), "v"(gg), "v"(b), "v"(alpha), "v"(om));
+      if (R.sa > thr) R.alive = false;
+    }
+    composite_group<K, I + 1, ZF>(P, R, exf, r, gg, b, alpha, thr);
+  } else if constexpr (I < K) {
     const float ri = group_lane<K, I>(r), gi = group_lane<K, I>(gg), bi = group_lane<K, I>(b),
                 ai = group_lane<K, I>(alpha);
     // sample I of the group exists iff group lane I's does (the existing samples are a prefix)
@@ -735,7 +763,15 @@ __device__ __forceinline__ void march(const RenderParams &P, float *L, int lane,
       // so that the test and its flag are not carried through the samples of a whole chunk
       auto samples = [&](auto wc) {
       constexpr bool WC = decltype(wc)::value;
-      for (int k = 0; k < S && R.alive; k += K) {
+      // The loop runs on a wave-uniform condition (S is the wave's: plan_chunk decides it on wave
+      // reductions) and a finished ray skips the body, instead of `k < S && R.alive` per lane: each lane
+      // takes the same samples, but the ray state is updated in place under the body's mask -- a
+      // per-lane loop exit makes the compiler copy the live-out values at the loop header every
+      // iteration and keep the exit masks' books in SALU (8 v_mov_b32 and 10 SALU per lit iteration,
+      // tools/isa_hot.py), and the depth-lane sums could not be accumulated in place (composite_group).
+      for (int k = 0, Su = __builtin_amdgcn_readfirstlane(S); k < Su; k += K) {
+        if (!__any(R.alive)) break;
+        if (!R.alive) continue;
         float r = 0.f, gg = 0.f, b = 0.f, alpha = 0.f;
         bool ex = R.mine, take = R.mine;
         if (SLAB && !inside) {
@@ -927,7 +963,8 @@ __global__ __launch_bounds__(64 * VR_WG_WAVES, march_min_eu(CAP, SCHED)) void ma
   else
     march<K, MODE, AB_ALIAS, COUNT, SHARE2, BIG, true, CAP>(P, L, lane, R, C);
 
-  if (active && (lane & (K - 1)) == 0) {
+  // (the lane index formed afresh: `lane` is not kept in a register across the march for this test)
+  if (active && (__lane_id() & (K - 1)) == 0) {
     const size_t plane = (size_t)P.plane_cols * (size_t)P.height;
     const size_t kk = (size_t)lc * (size_t)P.height + (size_t)y;
     out[kk] = R.sr;

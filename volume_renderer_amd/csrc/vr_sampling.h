@@ -37,6 +37,18 @@ struct Ax {
 __device__ __forceinline__ float weight8(float xb, float fl) {
   return fmaf(rintf(xb * 256.f), 1.f / 256.f, -fl);
 }
+// The same weights without v_rndne (a slow-class instruction), for arguments of known
+// range: the fp32 grid of [2^15, 2^16) is the multiples of 1/256, so for |x| < 2^14 the sum
+// x + 1.5 * 2^15 is rounded to 49152 + rint(256 x) / 256 (ties to even: 49152 * 256 is even), and
+// taking the constant off again is exact.  Two plain adds with a literal operand (VOP2): no
+// constant is held in a register across the sample loop.  Bit-identical to the rintf forms, the sign
+// of a zero result included (tools/microbench/weight8_check.c: every fp32 of [0, 1] and of
+// [-0.5, 1100]).
+//   frac8_rn(r): r in [0, 1] (any finite xb - floor(xb));
+//   weight8_rn(xb, fl): finite xb with |xb| < 2^14 (the last subtraction is exact, as weight8's fma).
+#define VR_RN_MAGIC 49152.f
+__device__ __forceinline__ float frac8_rn(float r) { return (r + VR_RN_MAGIC) - VR_RN_MAGIC; }
+__device__ __forceinline__ float weight8_rn(float xb, float fl) { return ((xb + VR_RN_MAGIC) - VR_RN_MAGIC) - fl; }
 template <bool NANCHK = true>
 __device__ __forceinline__ Ax axis(float c, int n, float fn) {
   if (NANCHK) c = (c != c) ? 0.f : c;  // NaN coordinate -> 0
@@ -74,7 +86,8 @@ __device__ __forceinline__ AxS axis_raw_s(float c, float fn) {
   const float xb = c * fn - 0.5f;
   const float fl = floorf(xb);
   const float r = xb - fl;
-  const float w = rintf(r * 256.f) * (1.f / 256.f);
+  // NANCHK = false: the coordinate is finite, so r is in [0, 1] (frac8_rn's range)
+  const float w = NANCHK ? rintf(r * 256.f) * (1.f / 256.f) : frac8_rn(r);
   return AxS{(int)fl, w, r >= 0.5f};
 }
 // axis_raw_s of a power-of-two cube (box [-1, 1]: bmin = -1, bscale = 1/2; n = 2 hs a power of
@@ -89,7 +102,8 @@ __device__ __forceinline__ AxS axis_cube_s(float p, float hs) {
   const float xb = fmaf(a, hs, -0.5f);
   const float fl = floorf(xb);
   const float r = xb - fl;
-  const float w = rintf(r * 256.f) * (1.f / 256.f);
+  // NANCHK = false: the coordinate is finite, so r is in [0, 1] (frac8_rn's range)
+  const float w = NANCHK ? rintf(r * 256.f) * (1.f / 256.f) : frac8_rn(r);
   return AxS{(int)fl, w, r >= 0.5f};
 }
 
@@ -179,12 +193,14 @@ struct AxF {
 // that is NaN or rounds past +-1).  One v_med3 does the NaN -> 0 substitution (the median of NaN,
 // 0 and 1 is min3 = 0 under the hardware's NaN rule) and keeps c in [0, 1], where the floor of
 // c*n - 0.5 is already in [-1, n-1]: the same axis as axis_f, without its compare, select and clamp.
-template <bool FMA = false>
+// RN8: the axis has at most 8192 texels (a tame launch's LUT, vr_capi.hip lut_ok), so xb lies in
+// [-0.5, 8192) and the weight is formed without v_rndne (weight8_rn).
+template <bool FMA = false, bool RN8 = false>
 __device__ __forceinline__ AxF axis_lut(float c, float fn) {
   c = __builtin_amdgcn_fmed3f(c, 0.f, 1.f);
   const float xb = FMA ? fmaf(c, fn, -0.5f) : c * fn - 0.5f;  // FMA: the fast variant's shading
   const float fl = floorf(xb);
-  return AxF{fl, weight8(xb, fl)};
+  return AxF{fl, RN8 ? weight8_rn(xb, fl) : weight8(xb, fl)};
 }
 
 // Trilinear fetch from a texture of fewer than 2^22 padded voxels (the illumination LUT): the
@@ -743,7 +759,7 @@ __device__ __forceinline__ void shade_fast(const RenderParams &P, const f3 g, co
   };
   if constexpr (NEED) need = lip2 < VR_HYB_TA * li2;
   const float alpha_n = acospi_f(dot3(n, li) * (rn * rsq_c(li2)));
-  const AxF la = axis_lut<true>(alpha_n, P.lut.fnx);
+  const AxF la = axis_lut<true, TAME>(alpha_n, P.lut.fnx);
   int i = 0;
   if (TAME || (P.lut.p != nullptr && P.lut.small && !P.lut.one)) {
     // the common LUT (bound, below 2^22 padded voxels): one wave-uniform test for the frame's
@@ -767,11 +783,11 @@ __device__ __forceinline__ void shade_fast(const RenderParams &P, const f3 g, co
       light1 = beta1 + gamma1 + la.w;
 #else
       if (TAME && VR_LUT_ZPAIR)  // the host binds a tame launch's LUT with its z-paired copy
-        fetch_small2_z(P.lut, la, axis_lut<true>(beta0, P.lut.fny), axis_lut<true>(gamma0, P.lut.fnz),
-                       axis_lut<true>(beta1, P.lut.fny), axis_lut<true>(gamma1, P.lut.fnz), light0, light1);
+        fetch_small2_z(P.lut, la, axis_lut<true, TAME>(beta0, P.lut.fny), axis_lut<true, TAME>(gamma0, P.lut.fnz),
+                       axis_lut<true, TAME>(beta1, P.lut.fny), axis_lut<true, TAME>(gamma1, P.lut.fnz), light0, light1);
       else
-        fetch_small2(P.lut, la, axis_lut<true>(beta0, P.lut.fny), axis_lut<true>(gamma0, P.lut.fnz),
-                     axis_lut<true>(beta1, P.lut.fny), axis_lut<true>(gamma1, P.lut.fnz), light0, light1);
+        fetch_small2(P.lut, la, axis_lut<true, TAME>(beta0, P.lut.fny), axis_lut<true, TAME>(gamma0, P.lut.fnz),
+                     axis_lut<true, TAME>(beta1, P.lut.fny), axis_lut<true, TAME>(gamma1, P.lut.fnz), light0, light1);
 #endif
       const float rl0 = refl * light0;
       ir = fmaf(rl0 * L0.cr, P.color[0], ir);
@@ -812,10 +828,10 @@ __device__ __forceinline__ void shade_fast(const RenderParams &P, const f3 g, co
     const f3 lop = mk(fmaf(-dlo, n.x, lo.x), fmaf(-dlo, n.y, lo.y), fmaf(-dlo, n.z, lo.z));
     const float beta = acospi_f(dlo * (rn * rsq_c(dot3(lo, lo))));
     const float gamma = acospi_f(gamma_q(lo, lop));
-    const float rl = refl * (TAME ? (VR_LUT_ZPAIR ? fetch_small_z(P.lut, la, axis_lut<true>(beta, P.lut.fny),
-                                                                 axis_lut<true>(gamma, P.lut.fnz))
-                                                  : fetch_small(P.lut, la, axis_lut<true>(beta, P.lut.fny),
-                                                                axis_lut<true>(gamma, P.lut.fnz)))
+    const float rl = refl * (TAME ? (VR_LUT_ZPAIR ? fetch_small_z(P.lut, la, axis_lut<true, TAME>(beta, P.lut.fny),
+                                                                 axis_lut<true, TAME>(gamma, P.lut.fnz))
+                                                  : fetch_small(P.lut, la, axis_lut<true, TAME>(beta, P.lut.fny),
+                                                                axis_lut<true, TAME>(gamma, P.lut.fnz)))
                                   : lut_light<true>(P.lut, la, beta, gamma));
     ir = fmaf(rl * L.cr, P.color[0], ir);
     ig = fmaf(rl * L.cg, P.color[1], ig);
