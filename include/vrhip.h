@@ -311,6 +311,75 @@ int vr_render_isosurface_device(vr_context *h, const vr_render_args *args, float
                                 float *d_out, float *d_depth, float *d_normal,
                                 unsigned long long *d_steps /* 3 counters, may be NULL */, void *stream);
 
+/* --- transfer-function render: a colormap and an alphamap per sample (no reference counterpart) ---
+ * 'render' with a classification: each sample's colour comes from a colormap instead of the constant
+ * color, and its opacity optionally from an alphamap -- what MATLAB's volshow calls Colormap and
+ * Alphamap over a data range -- and the accumulated opacity is an output plane.
+ * Table lookup L(T, n, lo, hi, c), in fp32, every operation rounded once:
+ *   inv = 1.0f / (hi - lo), formed once on the host;
+ *   x = ((c - lo) * inv) * (float)(n - 1);
+ *   x = fminf(fmaxf(x, 0.0f), (float)(n - 1)), where a NaN coordinate and -0 give +0: the coordinate
+ *       clamps at both ends and a NaN reads entry 0;
+ *   i = min((int)x, n - 2);  w = x - (float)i;  the value is fmaf(w, T[i+1] - T[i], T[i]).
+ * A constant table returns its constant bit for bit for every c (a constant -0 reads +0).  The kernel
+ * and vr_transfer_lookup_host evaluate one shared inline function (csrc/vr_transfer.h).
+ * The ray is exactly that of 'render': the same pixel-to-ray mapping and box intersection, tnear
+ * clamped to 0, tstep, t += tstep and pos += step, the max_steps cap, and render's exit tests in
+ * their order -- the accumulated opacity above opacity_threshold after compositing, then the cap,
+ * then t > tfar.  props[0] is honoured.
+ * The sample is that of 'render' with exact (oracle-order) shading, with two substitutions.  em_s and
+ * ab_s are render's emission and absorption samples (slot indices, the alias rule, the unbound and
+ * 1x1x1 cases).  cc = coord == VR_TF_VALUE ? em_s : t, t the march's t at this sample;
+ * C_c = L(colormap plane c, n_color, clim, cc) for c = 0..2;  A = alphamap ? L(alphamap, n_alpha,
+ * alim, ab_s) : ab_s;  e = Fe * em_s, a = Fa * A, alpha = 1 - expf(-(a * tstep)), eds = e * tstep;
+ * ill is render's exact shading at the sample (the handle's gradient method, refl = Fr * reflection,
+ * args->color inside ill as in 'render'; without lights or without a LUT ill = 0);
+ *   r_c = fmaf(eds, C_c, ill_c) * alpha
+ * -- C_c stands where color[c] stands in 'render' -- and the four compositing fmas follow unchanged.
+ * So with a colormap whose every entry is color[c] and no alphamap the image is the exact-shading
+ * 'render' image bit for bit.  The lights and the illumination LUT are uploaded and checked as
+ * 'render' does (a typed LUT: VR_ERR_UNSUPPORTED) and stay the handle's light state; nothing else of
+ * the handle is written: a 'render' before and after gives the same bits.
+ * Outputs.  The image (the composited r, g, b) is laid out as 'render' writes it, whole or as a part;
+ * the alpha plane, the accumulated opacity, as the projections' aux plane ([H, W], resp.
+ * [max_cols][H]).  A ray that misses the box writes 0 to both; a degenerate frame (no emission volume
+ * synced) writes zeros everywhere.  Empty space is leaped through the emission texture's occupancy
+ * map where a leaped sample adds exactly 0 (absorption aliases emission and Fa * A(+-0) * tstep == 0;
+ * both planes bit-identical to the march without; VR_TF_NO_PROBE=1, a test switch, turns it off).
+ * Errors.  The table checks come first and need no device, each VR_ERR_ARGUMENT: tf or colormap NULL,
+ * an n outside 2..VR_TF_MAX_ENTRIES, a non-finite table entry, a non-finite limit or !(lo < hi) (alim
+ * only with an alphamap), an unknown coord.  A NULL out / d_out with a non-empty image is
+ * VR_ERR_ARGUMENT; a multi-device group handle is VR_ERR_UNSUPPORTED. */
+#define VR_TF_MAX_ENTRIES 1024
+enum vr_transfer_coord { VR_TF_VALUE = 0, VR_TF_DEPTH = 1 };
+typedef struct vr_transfer {
+  const float *colormap; /* host, n_color x 3 as MATLAB stores an N x 3 single matrix: colormap[c * n_color + i] */
+  int32_t n_color;       /* 2 .. VR_TF_MAX_ENTRIES */
+  float clim[2];         /* colour coordinate range, lo < hi, finite */
+  const float *alphamap; /* host, n_alpha values, or NULL: the opacity of 'render' (a = Fa * ab_s) */
+  int32_t n_alpha;       /* 2 .. VR_TF_MAX_ENTRIES when alphamap != NULL */
+  float alim[2];         /* absorption-sample range of the alphamap, lo < hi, finite */
+  int32_t coord;         /* vr_transfer_coord: what indexes the colormap */
+  int32_t reserved;
+} vr_transfer;
+
+/* Into the caller-owned host image out[H*W*3] and, if not NULL, out_alpha[H*W]. */
+int vr_render_transfer(vr_context *h, const vr_render_args *args, const vr_transfer *tf, float *out,
+                       float *out_alpha /* [H,W], may be NULL */);
+
+/* Into device memory on `stream` (asynchronous, as vr_render_device), the whole image or a part.
+ * d_steps, if not NULL, points to at least two counters: d_steps[0] += samples visited, leaped ones
+ * included; d_steps[1] += samples fetched. */
+int vr_render_transfer_device(vr_context *h, const vr_render_args *args, const vr_transfer *tf,
+                              const vr_partition *part, float *d_out, float *d_alpha /* may be NULL */,
+                              unsigned long long *d_steps /* 2 counters, may be NULL */, void *stream);
+
+/* The kernel's table lookup on the CPU (needs no device): out[k * m + j] = L(table plane k, n, lim,
+ * c[j]) for the ncomp planes table[k * n + i].  VR_ERR_ARGUMENT for a NULL pointer with m > 0, an n
+ * outside 2..VR_TF_MAX_ENTRIES, ncomp < 1, or limits that are not finite with lo < hi. */
+int vr_transfer_lookup_host(const float *table, int32_t n, int32_t ncomp, const float lim[2], const float *c,
+                            uint64_t m, float *out /* [ncomp][m] */);
+
 /* Number of columns a part owns for image width w. */
 int64_t vr_partition_columns(int64_t w, const vr_partition *part);
 

@@ -290,5 +290,46 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     if (nlhs > 2) plhs[2] = normal; else mxDestroyArray(normal);
     return;
   }
+  if (!strcmp(cmd, "render_transfer")) {
+    // volumeRender('render_transfer', h, <render args>, colormap [N 3], clim [lo hi], alphamap [M 1] | false,
+    // alim [lo hi], 'value' | 'depth') -> [img, alpha] (vr_render_transfer): 'render' with the sample's
+    // colour read from the colormap and, with an alphamap, its absorption from that table; alpha [H W]
+    // is the accumulated opacity
+    if (nlhs > 2) mexErrMsgTxt("Too many output arguments.");
+    if (nrhs < 16) mexErrMsgTxt("insufficient parameter!");
+    if (nrhs > 16) mexErrMsgTxt("render_transfer: too many input arguments");
+    const mxArray *cm = prhs[11], *am = prhs[13];
+    if (mxGetClassID(cm) != mxSINGLE_CLASS || mxIsComplex(cm) || mxGetNumberOfDimensions(cm) != 2 || mxGetN(cm) != 3)
+      mexErrMsgTxt("render_transfer: colormap must be a single N x 3 matrix");
+    vr_transfer tf{};
+    tf.colormap = static_cast<const float *>(mxGetData(cm));
+    tf.n_color = (int32_t)mxGetM(cm);
+    if (mxGetClassID(prhs[12]) != mxSINGLE_CLASS) mexErrMsgTxt("render_transfer: clim must be single [lo hi]");
+    memcpy(tf.clim, data_of<float>(prhs[12], 2, "render_transfer: clim must be single [lo hi]"), sizeof(tf.clim));
+    if (!mxIsClass(am, "logical")) {  // the logical false: the opacity of 'render'
+      if (mxGetClassID(am) != mxSINGLE_CLASS || mxIsComplex(am) || mxGetNumberOfDimensions(am) != 2 ||
+          (mxGetM(am) != 1 && mxGetN(am) != 1))
+        mexErrMsgTxt("render_transfer: alphamap must be a single vector or false");
+      tf.alphamap = static_cast<const float *>(mxGetData(am));
+      tf.n_alpha = (int32_t)mxGetNumberOfElements(am);
+      if (mxGetClassID(prhs[14]) != mxSINGLE_CLASS) mexErrMsgTxt("render_transfer: alim must be single [lo hi]");
+      memcpy(tf.alim, data_of<float>(prhs[14], 2, "render_transfer: alim must be single [lo hi]"), sizeof(tf.alim));
+    }
+    char coord[16];
+    if (mxGetString(prhs[15], coord, sizeof(coord))) mexErrMsgTxt("render_transfer: coord must be 'value' or 'depth'");
+    if (!strcmp(coord, "depth")) tf.coord = VR_TF_DEPTH;
+    else if (!strcmp(coord, "value")) tf.coord = VR_TF_VALUE;
+    else mexErrMsgTxt("render_transfer: coord must be 'value' or 'depth'");
+    vr_render_args a;
+    std::vector<vr_light> lights;
+    vr_volume illum{};
+    unpack_render(prhs + 2, a, lights, illum);
+    mxArray *img = new_image(a, 1);
+    mxArray *alpha = mxCreateNumericMatrix((mwSize)a.resolution[0], (mwSize)a.resolution[1], mxSINGLE_CLASS, mxREAL);
+    check(vr_render_transfer(h, &a, &tf, static_cast<float *>(mxGetData(img)), static_cast<float *>(mxGetData(alpha))));
+    plhs[0] = img;
+    if (nlhs > 1) plhs[1] = alpha; else mxDestroyArray(alpha);
+    return;
+  }
   mexErrMsgTxt(("Unknown command: " + std::string(cmd)).c_str());
 }

@@ -21,6 +21,9 @@ VR_F32, VR_U8, VR_U16, VR_I16, VR_F16 = 0, 1, 2, 3, 4
 VR_DTYPE_UNORM = 0x100
 # enum vr_projection
 VR_PROJ_MIP, VR_PROJ_SUM = 0, 1
+# enum vr_transfer_coord, VR_TF_MAX_ENTRIES
+VR_TF_VALUE, VR_TF_DEPTH = 0, 1
+VR_TF_MAX_ENTRIES = 1024
 
 
 class VrVolume(ctypes.Structure):
@@ -48,6 +51,12 @@ class VrSlab(ctypes.Structure):
 class VrPartition(ctypes.Structure):
     _fields_ = [("block_cols", c_int32), ("part", c_int32), ("num_parts", c_int32),
                 ("reserved", c_int32)]
+
+
+class VrTransfer(ctypes.Structure):
+    _fields_ = [("colormap", c_void_p), ("n_color", c_int32), ("clim", c_float * 2),
+                ("alphamap", c_void_p), ("n_alpha", c_int32), ("alim", c_float * 2),
+                ("coord", c_int32), ("reserved", c_int32)]
 
 
 class VrChannel(ctypes.Structure):
@@ -94,6 +103,10 @@ SIGNATURES = [
     ("vr_render_isosurface", c_int, [c_void_p, POINTER(VrRenderArgs), c_float, c_void_p, c_void_p, c_void_p]),
     ("vr_render_isosurface_device", c_int, [c_void_p, POINTER(VrRenderArgs), c_float, POINTER(VrPartition), c_void_p,
                                             c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("vr_render_transfer", c_int, [c_void_p, POINTER(VrRenderArgs), POINTER(VrTransfer), c_void_p, c_void_p]),
+    ("vr_render_transfer_device", c_int, [c_void_p, POINTER(VrRenderArgs), POINTER(VrTransfer), POINTER(VrPartition),
+                                          c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("vr_transfer_lookup_host", c_int, [c_void_p, c_int32, c_int32, POINTER(c_float), c_void_p, c_uint64, c_void_p]),
     ("vr_partition_columns", c_int64, [c_int64, POINTER(VrPartition)]),
     ("vr_assemble_partitions", c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int64, c_void_p,
                                        c_void_p]),

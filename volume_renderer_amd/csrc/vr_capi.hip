@@ -31,6 +31,7 @@
 #include "../../include/vrhip.h"
 #include "vr_device.h"
 #include "vr_resources.h"
+#include "vr_transfer.h"
 
 #ifndef VR_WITH_K8
 #define VR_WITH_K8 0  // the K = 8 march objects (diagnostic build, make DIAG=1)
@@ -52,6 +53,11 @@ hipError_t launch_render(const RenderParams &P, int mode, bool ab_alias, bool bi
 hipError_t launch_project(const RenderParams &P, int mode, float *aux, bool big, bool probe, hipStream_t s);
 hipError_t launch_isosurface(const RenderParams &P, int grad, float level, float *depth, float *normal, bool big,
                              bool probe, hipStream_t s);
+// vr_transfer.hip: tab = the segment records of transfer_table_units(nc, na) 16-byte units
+uint32_t transfer_table_units(int32_t nc, int32_t na);
+hipError_t launch_transfer(const RenderParams &P, int grad, const float *tab, int32_t nc, int32_t na, float clo,
+                           float cinv, float alo, float ainv, int32_t coord, bool ab_alias, float *alpha, bool big,
+                           bool probe, hipStream_t s);
 // vr_march.hip built with VR_MARCH_FAST=1 / 0 (namespaces fast / exact) and VR_MARCH_K = 1, 2, 4, 8
 #define VR_DECL_MARCH(ns)                                                                                 \
   namespace ns {                                                                                         \
@@ -1684,6 +1690,178 @@ int do_isosurface(vr_context *h, const vr_render_args *a, float level, const vr_
   return VR_OK;
 }
 
+// The table checks of vr_render_transfer (include/vrhip.h): before the handle, no device needed.
+int check_table(const float *t, int32_t n, int32_t planes, const float lim[2], const char *what) {
+  if (n < 2 || n > VR_TF_MAX_ENTRIES)
+    return fail(VR_ERR_ARGUMENT, std::string(what) + ": 2 .. " + std::to_string(VR_TF_MAX_ENTRIES) + " entries");
+  for (int64_t i = 0; i < (int64_t)n * planes; ++i)
+    if (!std::isfinite(t[i])) return fail(VR_ERR_ARGUMENT, std::string(what) + ": non-finite entry");
+  if (!std::isfinite(lim[0]) || !std::isfinite(lim[1]) || !(lim[0] < lim[1]))
+    return fail(VR_ERR_ARGUMENT, std::string(what) + ": limits must be finite with lo < hi");
+  return VR_OK;
+}
+int check_transfer(const vr_transfer *tf) {
+  if (!tf || !tf->colormap) return fail(VR_ERR_ARGUMENT, "transfer function / colormap is NULL");
+  if (int rc = check_table(tf->colormap, tf->n_color, 3, tf->clim, "colormap")) return rc;
+  if (tf->alphamap)
+    if (int rc = check_table(tf->alphamap, tf->n_alpha, 1, tf->alim, "alphamap")) return rc;
+  if (tf->coord != VR_TF_VALUE && tf->coord != VR_TF_DEPTH) return fail(VR_ERR_ARGUMENT, "unknown colormap coordinate");
+  return VR_OK;
+}
+
+// L(T, n, lim, c) on the host: the kernel's lookup (vr_transfer.h) on the segment record of c
+float transfer_lookup(const float *T, int32_t n, const float lim[2], float c) {
+  const float inv = 1.0f / (lim[1] - lim[0]);
+  float w;
+  const int32_t i = vr_tf_segment(c, lim[0], inv, n, &w);
+  return vr_tf_value(w, T[i], T[i + 1] - T[i]);
+}
+
+// Staging ring of the transfer render's constants (segment records + light list) above the 4 KiB slots
+// of vr_host::ConstRing -- a 256-entry colormap is 8160 B, the largest tables 40 920 B: pinned host slots
+// and their device twins, a slot copied with hipMemcpyAsync on the launch's stream and rewritten only
+// after the launch that last read it completed (its event), as ConstRing does.  No allocation, no
+// null-stream copy per frame.  16 slots: a caller may have that many transfer launches in flight
+// before the host waits for the oldest.
+struct TableRing {
+  static constexpr size_t SLOT = 48 * 1024;
+  static constexpr unsigned N = 16;
+  char *host = nullptr, *dev = nullptr;
+  vr_host::EventPtr ev[N];
+  unsigned next = 0;
+  hipError_t init() {
+    if (host && dev) return hipSuccess;
+    hipError_t rc = hipHostMalloc(reinterpret_cast<void **>(&host), SLOT * N, hipHostMallocDefault);
+    if (rc == hipSuccess) rc = vr_host::device_alloc(reinterpret_cast<void **>(&dev), SLOT * N);
+    if (rc != hipSuccess) {  // all or nothing: a later call retries
+      if (host) (void)hipHostFree(host);
+      host = nullptr;
+      dev = nullptr;
+    }
+    return rc;
+  }
+};
+std::map<int, TableRing> &table_rings() {
+  static std::map<int, TableRing> &r = *new std::map<int, TableRing>();  // never destroyed (see g_tex)
+  return r;
+}
+
+// Transfer-function render (vr_render_transfer, vr_transfer.hip): the lights and the LUT uploaded and
+// checked as do_isosurface does, the frame of build_frame, the partition fields of do_project.  The
+// tables travel as segment records {T[i], T[i+1] - T[i]} in the launch's staged constants, in front of
+// the light list: one copy ordered on the launch's stream, through ConstRing up to 4 KiB and through
+// TableRing above (only a light list that pushes the payload past 48 KiB takes LaunchRec's dedicated
+// allocation, as a render's would).  Only the handle's light and LUT state is written, as by a render.
+int do_transfer(vr_context *h, const vr_render_args *a, const vr_transfer *tf, const vr_partition *part, float *d_out,
+                float *d_alpha, unsigned long long *d_steps, hipStream_t stream) {
+  if (a->num_lights > 0 && !a->lights) return fail(VR_ERR_ARGUMENT, "lights is NULL");
+  if (a->num_lights >= 0)
+    if (int rc = check_dtype(a->illumination, true, "illumination volume")) return rc;
+  if (a->num_lights >= 0 && a->illumination) {
+    const uint64_t required = required_memory(h) +
+                              a->illumination->dims[0] * a->illumination->dims[1] * a->illumination->dims[2] * 4 +
+                              (uint64_t)a->num_lights * sizeof(vr::DevLight);
+    if (int rc = check_free_device_memory(required)) return rc;
+  }
+  upload_lights(h, a);
+  Frame F;
+  int rc = build_frame(h, a, F);
+  if (rc) return rc;
+  rc = validate_partition(part);
+  if (rc) return rc;
+  vr::RenderParams &P = F.P;
+  P.block_cols = part ? part->block_cols : std::max<int32_t>(P.width, 1);
+  P.part = part ? part->part : 0;
+  P.num_parts = part ? part->num_parts : 1;
+  P.part_cols = (int32_t)part_columns(P.width, P.block_cols, P.part, P.num_parts);
+  P.plane_cols = (int32_t)part_columns(P.width, P.block_cols, 0, P.num_parts);
+  P.out = d_out;
+  P.steps = d_steps;
+  P.tile_mode = 0;
+  P.views = 1;
+  P.fast_shade = 0;
+  if (P.lut.p == nullptr) P.num_lights = 0;  // no LUT: no illumination term
+  const size_t plane = (size_t)P.plane_cols * (size_t)P.height;
+  if (plane && !d_out) return fail(VR_ERR_ARGUMENT, "output is NULL");
+  if (F.degenerate) {  // no synced emission volume: zeros everywhere
+    if (plane) VR_HIP(hipMemsetAsync(d_out, 0, plane * 3 * sizeof(float), stream));
+    if (plane && d_alpha) VR_HIP(hipMemsetAsync(d_alpha, 0, plane * sizeof(float), stream));
+    return VR_OK;
+  }
+  const int grad = P.num_lights == 0 ? 0 : (g_tex.grad_method == G_LOOKUP ? 2 : 1);
+  const int32_t nc = tf->n_color, na = tf->alphamap ? tf->n_alpha : 0;
+  // the staged constants: the segment records (16-byte units), then the light list
+  const size_t tab_bytes = (size_t)vr::transfer_table_units(nc, na) * 16;
+  std::vector<float> blob((tab_bytes + g_tex.lights.size() * sizeof(vr::DevLight)) / sizeof(float), 0.f);
+  for (int32_t i = 0; i + 1 < nc; ++i) {
+    float *r = blob.data() + 8 * (size_t)i;  // {r, dr, g, dg}, {b, db, 0, 0}
+    for (int c = 0; c < 3; ++c) {
+      const float *T = tf->colormap + (size_t)c * (size_t)nc;
+      r[2 * c] = T[i];
+      r[2 * c + 1] = T[i + 1] - T[i];
+    }
+  }
+  for (int32_t i = 0; i + 1 < na; ++i) {
+    float *r = blob.data() + 8 * (size_t)(nc - 1) + 2 * (size_t)i;  // {A, dA}
+    r[0] = tf->alphamap[i];
+    r[1] = tf->alphamap[i + 1] - tf->alphamap[i];
+  }
+  if (!g_tex.lights.empty())
+    std::memcpy(reinterpret_cast<char *>(blob.data()) + tab_bytes, g_tex.lights.data(),
+                g_tex.lights.size() * sizeof(vr::DevLight));
+  const float cinv = 1.0f / (tf->clim[1] - tf->clim[0]);
+  const float ainv = na ? 1.0f / (tf->alim[1] - tf->alim[0]) : 0.f;
+  // Empty-space leap: only where a leaped sample (em = ab = +-0) adds exactly 0 -- the absorption
+  // sample is the emission sample, Fa * A(+-0) * tstep == 0 (alpha = 1 - exp(-0) = 0), Fe finite (the
+  // emission term is +-0 times a finite table entry) and, when lit, the shading term proven finite.
+  // As the projection and isosurface leaps, this takes the running sums for finite: table entries so
+  // large that sa overflows to +-inf would make (1 - sa) * 0 a NaN on the marched path only.
+  // VR_TF_NO_PROBE=1 (test switch): every sample fetched.
+  bool probe = P.occ != nullptr && F.ab_alias && std::isfinite(P.fe) && (grad == 0 || P.skip_empty) &&
+               !test_flag("VR_TF_NO_PROBE");
+  for (float z : {0.f, -0.f}) {
+    const float A = na ? transfer_lookup(tf->alphamap, na, tf->alim, z) : z;
+    probe = probe && (P.fa * A) * P.tstep == 0.f;
+  }
+  LaunchRec L;
+  L.stream = stream;
+  L.device = h->device;
+  bind_reads(L);
+  const void *d_blob = nullptr;
+  const size_t blob_bytes = blob.size() * sizeof(float);
+  TableRing *ring = nullptr;
+  int slot = -1;
+  if (blob_bytes > vr_host::ConstRing::SLOT && blob_bytes <= TableRing::SLOT) {
+    ring = &table_rings()[h->device];
+    VR_HIP(ring->init());
+    slot = (int)(ring->next++ % TableRing::N);
+    vr_host::wait(ring->ev[slot]);  // the launch that used this slot N launches ago
+    ring->ev[slot].reset();
+    char *hs = ring->host + (size_t)slot * TableRing::SLOT, *ds = ring->dev + (size_t)slot * TableRing::SLOT;
+    std::memcpy(hs, blob.data(), blob_bytes);
+    VR_HIP(hipMemcpyAsync(ds, hs, blob_bytes, hipMemcpyHostToDevice, stream));
+    d_blob = ds;
+  } else {
+    VR_HIP(L.stage(blob.data(), blob_bytes, &d_blob));
+  }
+  P.lights = reinterpret_cast<const vr::DevLight *>(static_cast<const char *>(d_blob) + tab_bytes);
+  const hipError_t le = vr::launch_transfer(P, grad, static_cast<const float *>(d_blob), nc, na, tf->clim[0], cinv,
+                                            na ? tf->alim[0] : 0.f, ainv, tf->coord, F.ab_alias, d_alpha, F.big, probe,
+                                            stream);
+  if (ring) {  // the slot is free again when everything enqueued so far (its copy, the launch) completed
+    vr_host::EventPtr ev;
+    const hipError_t re = vr_host::record_event(stream, ev);
+    if (re != hipSuccess) {  // cannot track: wait here instead
+      vr_host::consume(re, "record_event (transfer table slot; waited for instead)");
+      (void)hipStreamSynchronize(stream);
+    }
+    ring->ev[slot] = ev;
+  }
+  VR_HIP(le);
+  VR_HIP(L.finish());
+  return VR_OK;
+}
+
 // Sort-last slab render: the handle's emission volume holds planes
 // [z_first, z_first + d2) of a volume of depth `depth`; the frame is built for the whole volume
 // (box, step, gradient offsets) and the march takes the samples of [z0, z1) only.
@@ -2812,6 +2990,60 @@ int vr_render_isosurface(vr_context *h, const vr_render_args *a, float level, fl
   if (plane && out_normal) VR_HIP(hipMemcpy(out_normal, d_normal, 3 * plane, hipMemcpyDeviceToHost));
   return VR_OK;
   VR_GUARD_END
+}
+
+int vr_render_transfer_device(vr_context *h, const vr_render_args *a, const vr_transfer *tf, const vr_partition *part,
+                              float *d_out, float *d_alpha, unsigned long long *d_steps, void *stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (int rc = check_transfer(tf)) return rc;
+  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
+  if (!a) return fail(VR_ERR_ARGUMENT, "insufficient parameter!");
+  if (!h->children.empty()) return fail(VR_ERR_UNSUPPORTED, "vr_render_transfer_device: one-device handles only");
+  VR_GUARD_BEGIN
+  DeviceGuard dg(h->device);
+  vr_host::prune_retired();
+  return do_transfer(h, a, tf, part, d_out, d_alpha, d_steps, (hipStream_t)stream);
+  VR_GUARD_END
+}
+
+int vr_render_transfer(vr_context *h, const vr_render_args *a, const vr_transfer *tf, float *out, float *out_alpha) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (int rc = check_transfer(tf)) return rc;
+  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
+  if (!a) return fail(VR_ERR_ARGUMENT, "insufficient parameter!");
+  if (!h->children.empty()) return fail(VR_ERR_UNSUPPORTED, "vr_render_transfer: one-device handles only");
+  VR_GUARD_BEGIN
+  DeviceGuard dg(h->device);
+  vr_host::prune_retired();
+  // the image and, behind it, the alpha plane in the handle's output buffer
+  const size_t plane = (size_t)a->resolution[0] * (size_t)a->resolution[1] * sizeof(float);
+  const size_t bytes = 4 * plane;
+  if (plane && !out) return fail(VR_ERR_ARGUMENT, "output is NULL");
+  if (bytes > h->d_out_bytes) {
+    if (h->d_out) VR_HIP(hipFree(h->d_out));
+    h->d_out = nullptr;
+    h->d_out_bytes = 0;
+    VR_HIP(hipMalloc(&h->d_out, bytes));
+    h->d_out_bytes = bytes;
+  }
+  float *d_alpha = out_alpha ? h->d_out + 3 * (plane / sizeof(float)) : nullptr;
+  const int rc = do_transfer(h, a, tf, nullptr, h->d_out, d_alpha, nullptr, nullptr);
+  if (rc) return rc;
+  if (plane) VR_HIP(hipMemcpy(out, h->d_out, 3 * plane, hipMemcpyDeviceToHost));
+  if (plane && out_alpha) VR_HIP(hipMemcpy(out_alpha, d_alpha, plane, hipMemcpyDeviceToHost));
+  return VR_OK;
+  VR_GUARD_END
+}
+
+int vr_transfer_lookup_host(const float *table, int32_t n, int32_t ncomp, const float lim[2], const float *c,
+                            uint64_t m, float *out) {
+  if (n < 2 || n > VR_TF_MAX_ENTRIES || ncomp < 1) return fail(VR_ERR_ARGUMENT, "table: 2 .. 1024 entries, ncomp >= 1");
+  if (!lim || !std::isfinite(lim[0]) || !std::isfinite(lim[1]) || !(lim[0] < lim[1]))
+    return fail(VR_ERR_ARGUMENT, "table: limits must be finite with lo < hi");
+  if (m && (!table || !c || !out)) return fail(VR_ERR_ARGUMENT, "table / coordinates / output is NULL");
+  for (int32_t k = 0; k < ncomp; ++k)
+    for (uint64_t j = 0; j < m; ++j) out[(uint64_t)k * m + j] = transfer_lookup(table + (size_t)k * (size_t)n, n, lim, c[j]);
+  return VR_OK;
 }
 
 int64_t vr_partition_columns(int64_t w, const vr_partition *p) {

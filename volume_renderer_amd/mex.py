@@ -334,6 +334,69 @@ def render_isosurface_device(handle, ra: VrRenderArgs, level, d_out: int, d_dept
                                             ctypes.c_void_p(int(stream)) if stream else None))
 
 
+TRANSFER_COORDS = {"value": _lib.VR_TF_VALUE, "depth": _lib.VR_TF_DEPTH}
+
+
+def transfer(colormap, clim=(0, 1), alphamap=None, alim=(0, 1), coord="value"):
+    """The vr_transfer of a transfer-function render: colormap [N, 3] single (rows R G B, column-major
+    as MATLAB stores it), clim = [lo hi], alphamap [M] single or None / False (the opacity of
+    'render'), alim = [lo hi], coord 'value' | 'depth' (or a vr_transfer_coord code).  Returns
+    (VrTransfer, keep-alive list)."""
+    cm = np.asarray(colormap)
+    if cm.dtype != np.float32 or cm.ndim != 2 or cm.shape[1] != 3:
+        raise _lib.VrError(1, "render_transfer: colormap must be a single N x 3 matrix")
+    cm = np.asfortranarray(cm)
+    tf = _lib.VrTransfer()
+    tf.colormap = cm.ctypes.data
+    tf.n_color = cm.shape[0]
+    lim = _f32(clim, 2, "clim")
+    tf.clim[0], tf.clim[1] = lim[0], lim[1]
+    am = None
+    if alphamap is not None and not _is_false(alphamap):
+        am = np.asarray(alphamap)
+        if am.dtype != np.float32 or am.size != max(am.shape, default=0):
+            raise _lib.VrError(1, "render_transfer: alphamap must be a single vector or false")
+        am = np.ascontiguousarray(am.reshape(-1))
+        tf.alphamap = am.ctypes.data
+        tf.n_alpha = am.size
+        lim = _f32(alim, 2, "alim")
+        tf.alim[0], tf.alim[1] = lim[0], lim[1]
+    if isinstance(coord, str):
+        if coord.lower() not in TRANSFER_COORDS:
+            raise _lib.VrError(1, "unknown colormap coordinate")
+        tf.coord = TRANSFER_COORDS[coord.lower()]
+    else:
+        tf.coord = int(coord)
+    return tf, [cm, am]
+
+
+def render_transfer_device(handle, ra: VrRenderArgs, tf, d_out: int, d_alpha: int = 0, part=None, d_steps: int = 0,
+                           stream: int = 0) -> None:
+    """A transfer-function render into device memory (vr_render_transfer_device), asynchronous on
+    `stream`: tf from transfer(); d_alpha = 0: no alpha plane; d_steps: two counters, samples visited
+    and samples fetched."""
+    check(lib().vr_render_transfer_device(_handle(handle), ctypes.byref(ra), ctypes.byref(tf),
+                                          ctypes.byref(part) if part is not None else None,
+                                          ctypes.c_void_p(int(d_out)) if d_out else None,
+                                          ctypes.c_void_p(int(d_alpha)) if d_alpha else None,
+                                          ctypes.c_void_p(int(d_steps)) if d_steps else None,
+                                          ctypes.c_void_p(int(stream)) if stream else None))
+
+
+def transfer_lookup_host(table, lim, c) -> np.ndarray:
+    """vr_transfer_lookup_host: the kernel's table lookup on the CPU.  table [n] or [n, ncomp] single,
+    lim = [lo hi], c the coordinates; returns [ncomp, len(c)] (or [len(c)] for a vector table)."""
+    t = np.asarray(table, dtype=np.float32)
+    vec = t.ndim == 1
+    t = np.asfortranarray(t.reshape(t.shape[0], -1))
+    cc = np.ascontiguousarray(np.asarray(c, dtype=np.float32).reshape(-1))
+    out = np.empty((t.shape[1], cc.size), np.float32)
+    l2 = (ctypes.c_float * 2)(*[float(x) for x in _f32(lim, 2, "lim")])
+    check(lib().vr_transfer_lookup_host(t.ctypes.data, t.shape[0], t.shape[1], l2, cc.ctypes.data, cc.size,
+                                        out.ctypes.data))
+    return out[0] if vec else out
+
+
 def set_option(name: str, value: int) -> None:
     """vr_set_option: a process-wide library option (include/vrhip.h)."""
     check(lib().vr_set_option(name.encode(), int(value)))
@@ -470,8 +533,8 @@ def _group_devices():
 
 def volumeRender(cmd, *args):
     """The `volumeRender` mex: commands 'new', 'delete', 'mem_info', 'sync_volumes', 'render' (and
-    'render_stereo', 'render_channels', 'render_projection', 'render_isosurface', which the reference
-    does not have)."""
+    'render_stereo', 'render_channels', 'render_projection', 'render_isosurface', 'render_transfer',
+    which the reference does not have)."""
     nrhs = 1 + len(args)
     if not isinstance(cmd, str) or len(cmd) >= 64:
         raise _lib.VrError(1, "First input should be a command string less than 64 characters long.")
@@ -559,6 +622,21 @@ def volumeRender(cmd, *args):
                                      normal.ctypes.data_as(ctypes.c_void_p) if normal.size else None))
         del keep
         return out, depth, normal
+    if cmd == "render_transfer":  # ('render_transfer', h, <the nine render arguments>, colormap [N 3],
+        #                            clim [lo hi], alphamap [M 1] | false, alim [lo hi], 'value' | 'depth')
+        if nrhs < 16:
+            raise _lib.VrError(1, "insufficient parameter!")
+        tf, tkeep = transfer(args[10], args[11], args[12], args[13], args[14])
+        ra, keep = render_args(*args[1:10])
+        res = np.asarray(args[5]).reshape(-1)
+        H, W = int(res[0]), int(res[1])
+        out = np.zeros((H, W, 3), dtype=np.float32, order="F")
+        alpha = np.zeros((H, W), dtype=np.float32, order="F")
+        check(L.vr_render_transfer(h, ctypes.byref(ra), ctypes.byref(tf),
+                                   out.ctypes.data_as(ctypes.c_void_p) if out.size else None,
+                                   alpha.ctypes.data_as(ctypes.c_void_p) if alpha.size else None))
+        del keep, tkeep
+        return out, alpha
     if cmd == "render":
         if nrhs < 11:
             raise _lib.VrError(1, "insufficient parameter!")
