@@ -872,6 +872,8 @@ int build_frame(vr_context *h, const vr_render_args *a, Frame &F, uint64_t depth
     P.skip_empty = ok ? 1 : 0;
     if (const char *ev = test_env("VR_NO_EMPTY_SKIP"))  // A/B switch for measurements
       if (ev[0] == '1') P.skip_empty = 0;
+    // test switch: chunks are staged without asking the occupancy map first (vr_march.hip)
+    if (P.skip_empty && test_flag("VR_NO_BRICK_TEST")) P.skip_empty = 2;
   }
   // Per-sample range tests the upload statistics decide for the whole launch (vr_sampling.h): every
   // opacity argument |Fa * ab(p) * tstep| below 2^-7 (the exponential's Taylor form needs no

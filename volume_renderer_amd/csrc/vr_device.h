@@ -80,7 +80,9 @@ struct RenderParams {
   const float *gvec;              // lookup gradient interleaved, (gx, gy, gz, 0) per padded voxel, or null
   uint32_t gv_row8, gv_plane8;    // VR_GVEC_BRICK: entries per row / plane of 2x2x2 bricks (vr_sampling.h)
   int32_t re_is_em;               // reflection texture == emission texture (sample reused)
-  int32_t skip_empty;             // alpha == 0 samples may skip shading (exactly 0 contribution)
+  int32_t skip_empty;             // alpha == 0 samples may skip shading (exactly 0 contribution);
+                                  // 2 (test switch): likewise, the march does not ask the occupancy
+                                  // map about a chunk's box before staging it
   int32_t small_x;                // every |Fa * ab(p) * tstep| < 2^-7: opacity without a range test
   int32_t eds_finite;             // every |Fe * em(p) * tstep| finite: empty skip without its test
   // "tame" launch (the march's fast path, vr_march.hip): skip_empty, eds_finite and small_x hold,

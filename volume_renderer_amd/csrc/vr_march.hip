@@ -692,13 +692,28 @@ __device__ __forceinline__ void march(const RenderParams &P, float *L, int lane,
         }
       }
     }
+    // The occupancy map's answer before the copy (vr_stage.h box_bricks_empty, round 12): a whole
+    // box all of whose bricks are +-0 would stage all-zero, so the chunk takes the empty-chunk leap
+    // below unstaged.  Asked under the conditions under which the staging may set `empty`, and only
+    // where the wave is likely outside the data: ps == 0, i.e. after a failed probe and after every
+    // leap that follows it -- the chunks in front of a shell wall, staged "until they find data".
+    // Between data chunks (ps < 0) it is not asked: there one wasted copy per exit from the data
+    // costs less than a byte load in front of every data chunk (profiles/round12/README.md).
+    // (A PROBE march is a tame one, so P.skip_empty holds; the helper reads it afresh from the argument
+    // segment for the test switch VR_NO_BRICK_TEST, skip_empty == 2: held in an SGPR for this test it
+    // cost the lit loop two v_readlane.)
+    bool empty = false;
+    if constexpr (PROBE) {
+      if (staged && !partial && ps == 0)
+        empty = box_bricks_empty(kp, B.rx, B.ry, B.rz, B.ex, B.ey, B.ez, lane) > 0;
+    }
     if (COUNT && lane == 0) {  // diagnostics: box volume of partial/failed chunks, S of staged ones
       if (!staged || partial) atomicAdd(P.steps + 8 + min(box_vol >> 8, 31), 1ull);
       else atomicAdd(P.steps + 40 + (S >= 32 ? 0 : (S >= 16 ? 1 : (S >= 8 ? 2 : 3))), 1ull);
-      if (staged) atomicAdd(P.steps + 45, (unsigned long long)(B.pxy * B.ez));  // staging volume (floats)
+      if (staged && !empty) atomicAdd(P.steps + 45, (unsigned long long)(B.pxy * B.ez));  // staging volume (floats)
+      if (empty) atomicAdd(P.steps + 46, 1ull);  // chunks leaped on the map's word, without a copy
     }
-    bool empty = false;
-    if (staged) {
+    if (staged && !empty) {
       const bool nonzero = stage_box<BIG>(L, E, B, lane);  // always stage: the samples read the slot
       // leap only when the absorption texture is the staged one: a zero emission box says nothing
       // about the opacity of a separate absorption texture (the simEmAb slot path)

@@ -45,18 +45,27 @@ namespace vr {
 #define VR_ATTEMPTS 3    // box attempts per chunk: S = VR_CHUNK, /2, /4, ...
 #endif
 
+// A row rotation of v (DPP control 0x120 + n: row_ror:n) with every row and bank enabled: all 16
+// lanes of every row are written, so the instruction's `old` operand is dead and is left undefined
+// (mov_dpp) -- with old = v (update_dpp(v, v, ..)) the compiler copies v before each rotation,
+// since v stays live: 12 v_mov_b32 per box attempt of plan_chunk (round 12).
+template <int CTRL>
+__device__ __forceinline__ int row_ror(int v) {
+  return __builtin_amdgcn_mov_dpp(v, CTRL, 0xf, 0xf, false);
+}
+
 // Wave-wide min / max without LDS: DPP row rotations reduce each 16-lane row, then the gfx950
 // permlane16 / permlane32 swaps combine the rows (each returns both halves of the exchange, whose
 // min / max is the xor-16 / xor-32 partner's).  Result made wave-uniform.
 template <bool MAX>
 __device__ __forceinline__ int wave_reduce(int v) {
-  int o = __builtin_amdgcn_update_dpp(v, v, 0x128, 0xf, 0xf, false);  // row_ror:8
+  int o = row_ror<0x128>(v);
   v = MAX ? max(v, o) : min(v, o);
-  o = __builtin_amdgcn_update_dpp(v, v, 0x124, 0xf, 0xf, false);  // row_ror:4
+  o = row_ror<0x124>(v);
   v = MAX ? max(v, o) : min(v, o);
-  o = __builtin_amdgcn_update_dpp(v, v, 0x122, 0xf, 0xf, false);  // row_ror:2
+  o = row_ror<0x122>(v);
   v = MAX ? max(v, o) : min(v, o);
-  o = __builtin_amdgcn_update_dpp(v, v, 0x121, 0xf, 0xf, false);  // row_ror:1
+  o = row_ror<0x121>(v);
   v = MAX ? max(v, o) : min(v, o);
   const auto p16 = __builtin_amdgcn_permlane16_swap(v, v, false, false);
   v = MAX ? max((int)p16[0], (int)p16[1]) : min((int)p16[0], (int)p16[1]);
@@ -74,10 +83,10 @@ __device__ __forceinline__ int pk_min(int a, int b) {
   return __builtin_bit_cast(int, __builtin_elementwise_min(__builtin_bit_cast(vr_s2, a), __builtin_bit_cast(vr_s2, b)));
 }
 __device__ __forceinline__ int wave_min2(int v) {
-  v = pk_min(v, __builtin_amdgcn_update_dpp(v, v, 0x128, 0xf, 0xf, false));  // row_ror:8
-  v = pk_min(v, __builtin_amdgcn_update_dpp(v, v, 0x124, 0xf, 0xf, false));  // row_ror:4
-  v = pk_min(v, __builtin_amdgcn_update_dpp(v, v, 0x122, 0xf, 0xf, false));  // row_ror:2
-  v = pk_min(v, __builtin_amdgcn_update_dpp(v, v, 0x121, 0xf, 0xf, false));  // row_ror:1
+  v = pk_min(v, row_ror<0x128>(v));
+  v = pk_min(v, row_ror<0x124>(v));
+  v = pk_min(v, row_ror<0x122>(v));
+  v = pk_min(v, row_ror<0x121>(v));
   const auto p16 = __builtin_amdgcn_permlane16_swap(v, v, false, false);
   v = pk_min((int)p16[0], (int)p16[1]);
   const auto p32 = __builtin_amdgcn_permlane32_swap(v, v, false, false);
@@ -374,11 +383,11 @@ __device__ __forceinline__ bool stage_box(float *L, const DevTex &t, const Box &
     for (int j = 0; j < VR_STAGE_UNROLL; ++j) {
       if (k0 + j < n) {
         L[li[j]] = v[j];
-        acc |= __float_as_uint(v[j]) & 0x7fffffffu;
+        acc |= __float_as_uint(v[j]);
       }
     }
   }
-  return __any(acc != 0u);
+  return __any((acc & 0x7fffffffu) != 0u);  // (the sign bit masked once, after the OR: -0 is empty)
 }
 
 #ifndef VR_PARTIAL
@@ -546,6 +555,44 @@ __device__ __forceinline__ int probe_run(const RenderParams &P, KParams kp0, boo
       const int qy = (int)(((float)r + 0.5f) * rcx);
       const int qx = r - qy * cx;
       v |= occ[(uint32_t)(bz + qz) * obxy + (uint32_t)(by + qy) * obx + (uint32_t)(bx + qx)];
+    }
+  }
+  return __any(v != 0u) ? 0 : 1;
+}
+
+// The occupancy map's answer for a planned chunk box, before it is staged (round 12): whether every
+// brick that the box [r, r + e) touches holds only +-0.  The bricks cover a superset of the box and a
+// brick's byte is 0 only when all its voxels are +-0 (NaN counts as data, as in stage_box), so 1
+// implies that the staged OR would have been 0: the chunk may take the empty-chunk leap without the
+// copy.  The box is wave-uniform, so the brick ranges cost no VALU; one byte load per lane, a second
+// only for a box of 65 .. 128 bricks.  Returns 1: all empty, 0: a brick is occupied, -1: unknown (no
+// map, or more than 128 bricks).  Wave-uniform.  Inline: out of line (a call, its arguments made
+// scalars again) the lit loop grew by 6 VALU and the metric kernel ran 24.8-24.9 ms against 23.7
+// (profiles/round12/README.md).
+__device__ __forceinline__ int box_bricks_empty(KParams kp0, int rx, int ry, int rz, int ex, int ey, int ez, int lane) {
+  if (kp0 == nullptr) return -1;
+  const KParams kp = kparams_fresh(kp0);
+  const uint8_t *occ = kp->occ;
+  if (occ == nullptr || kp->skip_empty != 1) return -1;  // (2: the test switch VR_NO_BRICK_TEST)
+  const int bx = rx >> VR_OCC_LOG, by = ry >> VR_OCC_LOG, bz = rz >> VR_OCC_LOG;
+  const int cx = ((rx + ex - 1) >> VR_OCC_LOG) - bx + 1, cy = ((ry + ey - 1) >> VR_OCC_LOG) - by + 1,
+            cz = ((rz + ez - 1) >> VR_OCC_LOG) - bz + 1;
+  const int cnt = cx * cy * cz;
+  if (cnt > 128) return -1;
+  // lane q -> brick q (and q + 64) of the box, x fastest; the divisions by the uniform extents in fp32,
+  // as probe_run (q < 128 and extents <= 128: exact quotients after the truncation)
+  const uint32_t obx = kp->occ_bx, obxy = kp->occ_bxy;
+  const uint8_t *o0 = occ + ((uint32_t)bz * obxy + (uint32_t)by * obx + (uint32_t)bx);  // uniform
+  const float rcx = 1.f / (float)cx, rcy = 1.f / (float)cy;
+  uint32_t v = 0;
+  for (int j = 0; j < 2 && 64 * j < cnt; ++j) {  // (uniform trip count)
+    const int q = lane + 64 * j;
+    if (q < cnt) {
+      const int qz = (int)(((float)q + 0.5f) * (rcx * rcy));
+      const int r = q - qz * cx * cy;
+      const int qy = (int)(((float)r + 0.5f) * rcx);
+      const int qx = r - qy * cx;
+      v |= o0[(uint32_t)qz * obxy + (uint32_t)qy * obx + (uint32_t)qx];
     }
   }
   return __any(v != 0u) ? 0 : 1;
