@@ -821,6 +821,11 @@ int build_frame(vr_context *h, const vr_render_args *a, Frame &F, uint64_t depth
   P.gy = dev_tex(g_tex.bind[T_DY]);
   P.gz = dev_tex(g_tex.bind[T_DZ]);
   P.lut = dev_tex(g_tex.bind[T_LIGHT]);
+  // the z-paired copy's offsets are twice the plain LUT's (exact: integers below 2^25)
+  P.lutz_fpx8 = 2.f * P.lut.fpx4;
+  P.lutz_fpxy8 = 2.f * P.lut.fpxy4;
+  P.lutz_fbase8 = 2.f * P.lut.fbase4;
+  P.lutz_px8 = 8u * P.lut.px;
   P.num_lights = (int32_t)g_tex.lights.size();
   P.lights = nullptr;  // staged per launch on the launch's stream (stage_frame)
   F.mode = P.num_lights == 0 ? 0 : (g_tex.grad_method == G_LOOKUP ? 2 : 1);
@@ -915,6 +920,12 @@ int build_frame(vr_context *h, const vr_render_args *a, Frame &F, uint64_t depth
                                        (double)bmax[2] * bmax[2]));
   const double cap = 2.0 * diag / (double)P.tstep + 64.0;
   P.max_steps = (finite && cap < 2.0e9) ? (int32_t)cap : 2000000000;
+  // test switch: a lower cap, which ends rays inside the volume (and inside a chunk) -- the same for
+  // every kernel of the frame, so renders with it compare across kernels like any others
+  if (const char *ev = test_env("VR_MAX_STEPS")) {
+    const long v = std::strtol(ev, nullptr, 10);
+    if (v > 0 && v < (long)P.max_steps) P.max_steps = (int32_t)v;
+  }
   F.degenerate = !finite;  // no synced emission volume: nothing to march through (renders zeros)
   return VR_OK;
 }

@@ -75,6 +75,10 @@ struct RenderParams {
                                   // variant derives the taps from the centre, vr_sampling.h)
   float cube_hs[3];               // tap_half: n / 2 per axis of the power-of-two box [-1, 1]^3 (axis_cube_s)
   int32_t num_lights;
+  // The LUT's byte-offset terms for its z-paired copy (lut.zp, 8-byte entries; vr_sampling.h
+  // fetch_small_z): 8*px here, 8*pxy and 8*(pxy+px+1) below -- twice lut.fpx4, fpxy4 and fbase4, each
+  // in one of the struct's 4-byte alignment holes, so that it does not grow (RenderViews below).
+  float lutz_fpx8;
   const DevLight *lights;
   DevTex em, ab, re, gem, gx, gy, gz, lut;
   const float *gvec;              // lookup gradient interleaved, (gx, gy, gz, 0) per padded voxel, or null
@@ -106,6 +110,7 @@ struct RenderParams {
   int32_t pair_shift;             // views 2: 0 (each workgroup one eye), or paired tiles -- a wave
                                   // marches the right eye's columns c.. with the left eye's c + shift..
   uint32_t view_blocks;           // workgroups per view (the launch has views x view_blocks)
+  float lutz_fpxy8;               // (see lutz_fpx8)
   // launch schedule: workgroup b marches tile block wg_order[b] (null: b); each
   // block's duration in s_memrealtime ticks is stored to wg_cost[block] (null: not recorded)
   const uint32_t *wg_order;
@@ -117,6 +122,7 @@ struct RenderParams {
                                   // 2 following the last measured order without timing
   uint32_t prio_blocks;           // scheduled launch: the first prio_blocks workgroups (the longest)
                                   // run at raised wave priority
+  float lutz_fbase8;              // (see lutz_fpx8)
   // empty-space probe (round 5, vr_stage.h probe_run): the emission texture's occupancy map -- one
   // byte per 8x8x8 brick of the padded volume, 0 when every voxel of the brick is +-0 -- or null;
   // its row and plane pitch in bricks; per axis the probe's margin in texels (the centre taps'
@@ -124,6 +130,7 @@ struct RenderParams {
   const uint8_t *occ;
   uint32_t occ_bx, occ_bxy;
   float probe_off[3];
+  uint32_t lutz_px8;              // 8 * lut.px: the byte pitch of a row of lut.zp (see lutz_fpx8)
   unsigned long long *steps;      // optional sample counter
   // sort-last slab launch (vr_render_slab): owned normalized z range [slab_z0,
   // slab_z1), the margin of the chunk ownership test, the resident padded planes [slab_pk0,

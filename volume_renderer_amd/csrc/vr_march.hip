@@ -200,7 +200,8 @@ struct ChunkStats {
 // One sample of a ray at position `pos` (volumeRender_kernel.cu:444-474): the emission /
 // absorption fetch, opacity, and for a lit, non-empty sample the gradient and the shading.  Returns
 // the premultiplied colour (r, g, b) and the opacity; `shaded` says whether shading ran.
-template <int MODE, bool AB_ALIAS, bool SHARE2, bool BIG, bool NANCHK, int NL = 0>
+// WHOLE_CT: `whole` is true at compile time (the whole-chunk copy of the depth-lane sample loop).
+template <int MODE, bool AB_ALIAS, bool SHARE2, bool BIG, bool NANCHK, int NL = 0, bool WHOLE_CT = false>
 __device__ __forceinline__ void sample_at(const RenderParams &P, const float *L, const Box &B, bool staged, bool whole,
                                           const f3 pos, const f3 o, float &r, float &gg, float &b, float &alpha,
                                           bool &shaded, float rv = 0.f, const DevLight *pre = nullptr) {
@@ -239,13 +240,38 @@ __device__ __forceinline__ void sample_at(const RenderParams &P, const float *L,
     az = axis_raw<NANCHK>(ps.z, E.fnz);
   }
   // centre cell in the slot; the gradient taps below differ from it along one axis only
-  const int lx = slot_coord(ax.i, B.rx), ly = slot_coord(ay.i, B.ry), lz = slot_coord(az.i, B.rz);
+  // A whole chunk's half-texel sample (FOLD) needs the slot coordinates only for the centre cell's
+  // address, so the box origin and the slot's base are folded out of it: the LDS byte address
+  // L + 4 ((iz + 1 - rz) pxy + (iy + 1 - ry) px + (ix + 1 - rx)) is 4 pxy iz + 4 px iy + 4 ix + kfold
+  // mod 2^32, kfold wave-uniform (SALU, once per chunk: the slot base is the wave's).  The products
+  // as 24-bit multiplies: a whole box holds every tap, so |i| <= n < 16000, and 4 px, 4 pxy are at
+  // most the slot's bytes (< 2^14) -- both factors fit 24 bits and the product 32.  The address is
+  // opaque to the compiler, so that every tap is this one register plus a pitch (it otherwise keeps
+  // the offset and three copies of the base apart, and adds a base to each of the 14 reads' rows).
+  constexpr bool FOLD =
+      WHOLE_CT && VR_MARCH_FAST && MODE == 1 && SHARE2 && VR_MERGED_BOUNDS && VR_WHOLE_BOX && !VR_CHECK_WHOLE;
+  const int lx = FOLD ? 0 : slot_coord(ax.i, B.rx), ly = FOLD ? 0 : slot_coord(ay.i, B.ry),
+            lz = FOLD ? 0 : slot_coord(az.i, B.rz);
   // (the per-axis box tests, evaluated where used: only the paths that are not wholly staged need them)
 #define inx in_box(lx, B.ex)
 #define iny in_box(ly, B.ey)
 #define inz in_box(lz, B.ez)
   const int ayz = lz * B.pxy + ly * B.px;  // slot word of (0, ly, lz)
   const int ac = ayz + lx;
+  lds_cptr cc;  // the centre cell in the slot (HALF_TAPS)
+  if constexpr (FOLD) {
+    uint32_t kfold = __builtin_amdgcn_readfirstlane(lds_addr(L)) +
+                     4u * (uint32_t)((1 - B.rz) * B.pxy + (1 - B.ry) * B.px + (1 - B.rx));
+    asm("" : "+s"(kfold));  // (one scalar: the compiler otherwise adds the box's part and the base apart;
+                            // the slot base is wave-uniform, and already a scalar in march_kernel)
+    uint32_t a4 = ((uint32_t)ax.i << 2) + kfold;
+    // one multiply-add per pitch (written out: the compiler takes two multiplies and a v_add3_u32)
+    asm("v_mad_i32_i24 %0, %1, %2, %0" : "+v"(a4) : "v"(ay.i), "s"(4 * B.px));
+    asm("v_mad_i32_i24 %0, %1, %2, %0" : "+v"(a4) : "v"(az.i), "s"(4 * B.pxy));
+    cc = (lds_cptr)a4;
+  } else {
+    cc = lds_cell(L, ac);
+  }
   Cell C;  // the centre's partial sums, for the half-texel taps (valid where the centre is staged)
   float em_s;
   // The half-texel taps of every lane in the slot (cells a - 1 .. a + 1 per axis, a = i + hi): then
@@ -270,8 +296,8 @@ __device__ __forceinline__ void sample_at(const RenderParams &P, const float *L,
     }
   }
   if constexpr (HALF_TAPS) {
-    if (full) em_s = lds_tri_cell(L, B, ac, ax.w, ay.w, az.w, C);
-    else if (staged && inx && iny && inz) em_s = lds_tri_cell(L, B, ac, ax.w, ay.w, az.w, C);
+    if (full) em_s = lds_tri_cell(cc, B, ax.w, ay.w, az.w, C);
+    else if (staged && inx && iny && inz) em_s = lds_tri_cell(cc, B, ax.w, ay.w, az.w, C);
     else {
       const DevTex U = reload(E);
       em_s = fetch<BIG>(U, clamp_ax(ax, U.nx), clamp_ax(ay, U.ny), clamp_ax(az, U.nz));
@@ -305,7 +331,7 @@ __device__ __forceinline__ void sample_at(const RenderParams &P, const float *L,
       // a = i + hi): the taps from the slot with their shared voxels and partial sums
       // unhalved: the fast shading uses g only through n = -g * rsq(g.g), which the exact factor 2
       // leaves bit-identical (4x scales g.g by a power of two; rsq halves exactly)
-      g = half_grad_lds(L, B, ac, sx, sy, sz, ax.w, ay.w, az.w, C);
+      g = half_grad_lds(cc, B, sx, sy, sz, ax.w, ay.w, az.w, C);
     } else if (HALF_TAPS && (HALF_ONLY || P.tap_half)) {
       // fast variant, gradient offset of exactly half a texel on every axis (a power-of-two cube,
       // vr_capi.hip half_texel_taps): each axis' two taps derived from the centre's (half_taps);
@@ -420,6 +446,22 @@ __device__ __forceinline__ bool group_any(bool b) {
   }
 }
 
+// group_any on a lane mask of the wave (a ballot), K = 2 or 4: bit l of the result is set when any bit
+// of lane l's K-lane group is set in m.  Scalar shifts and masks of the 64-bit word.
+template <int K>
+__device__ __forceinline__ uint64_t group_or_mask(uint64_t m) {
+  static_assert(K == 2 || K == 4, "lane groups of 2 or 4");
+  if constexpr (K == 2) {
+    const uint64_t x = (m | (m >> 1)) & 0x5555555555555555ull;  // the group's OR in its lowest lane's bit
+    return x | (x << 1);
+  } else {
+    uint64_t x = m | (m >> 1);
+    x = (x | (x >> 2)) & 0x1111111111111111ull;
+    x |= x << 1;
+    return x | (x << 2);
+  }
+}
+
 // The largest v over this lane's K-lane group (called by whole groups): acc = v to start.
 template <int K, int I = 0>
 __device__ __forceinline__ int group_max_i(int v, int acc) {
@@ -441,16 +483,16 @@ __device__ __forceinline__ int group_max_i(int v, int acc) {
 #define VR_ZERO_FILL 1
 #endif
 template <int K, int I, bool ZF = false>
-__device__ __forceinline__ void composite_group(const RenderParams &P, Ray &R, float exf, float r, float gg, float b,
-                                                float alpha, float thr) {
+__device__ __forceinline__ void composite_group(const RenderParams &P, Ray &R, bool &alive, float exf, float r, float gg,
+                                                float b, float alpha, float thr) {
   if constexpr (K == 2 && ZF && I < K) {
     // the tame two-lane group: sum = fma(1 - sum.a, sample I, sum) as v_fmac_f32 with the sample read
     // through its DPP operand -- one slow-class instruction per sum where the move and the fma are a
     // slow and a fast one (tools/microbench/valu_rates.hip).  The same fused multiply-add, in place.
-    // Both lanes of a pair are enabled together here (R.alive is the ray's), so the source lane is
+    // Both lanes of a pair are enabled together here (`alive` is the ray's), so the source lane is
     // never a disabled one.  A DPP read of a VGPR that the preceding VALU instruction wrote owes two
     // wait states, and the compiler does not look into the asm: the s_nop 1 pays them.
-    if (R.alive) {
+    if (alive) {
       const float om = 1.f - R.sa;
       if constexpr (I == 0)
         asm("s_nop 1\n\t"
@@ -468,22 +510,22 @@ __device__ __forceinline__ void composite_group(const RenderParams &P, Ray &R, f
             "v_fmac_f32_dpp %3, %7, %8 quad_perm:[1,1,3,3] row_mask:0xf bank_mask:0xf"
             : "+v"(R.sr), "+v"(R.sg), "+v"(R.sb), "+v"(R.sa)
             : "v"(r), "v"(gg), "v"(b), "v"(alpha), "v"(om));
-      if (R.sa > thr) R.alive = false;
+      if (R.sa > thr) alive = false;
     }
-    composite_group<K, I + 1, ZF>(P, R, exf, r, gg, b, alpha, thr);
+    composite_group<K, I + 1, ZF>(P, R, alive, exf, r, gg, b, alpha, thr);
   } else if constexpr (I < K) {
     const float ri = group_lane<K, I>(r), gi = group_lane<K, I>(gg), bi = group_lane<K, I>(b),
                 ai = group_lane<K, I>(alpha);
     // sample I of the group exists iff group lane I's does (the existing samples are a prefix)
-    if ((ZF || group_lane<K, I>(exf) != 0.f) && R.alive) {
+    if ((ZF || group_lane<K, I>(exf) != 0.f) && alive) {
       const float om = 1.f - R.sa;
       R.sr = fmaf(om, ri, R.sr);
       R.sg = fmaf(om, gi, R.sg);
       R.sb = fmaf(om, bi, R.sb);
       R.sa = fmaf(om, ai, R.sa);
-      if (R.sa > thr) R.alive = false;
+      if (R.sa > thr) alive = false;
     }
-    composite_group<K, I + 1, ZF>(P, R, exf, r, gg, b, alpha, thr);
+    composite_group<K, I + 1, ZF>(P, R, alive, exf, r, gg, b, alpha, thr);
   }
 }
 
@@ -784,6 +826,44 @@ __device__ __forceinline__ void march(const RenderParams &P, float *L, int lane,
       // per-lane loop exit makes the compiler copy the live-out values at the loop header every
       // iteration and keep the exit masks' books in SALU (8 v_mov_b32 and 10 SALU per lit iteration,
       // tools/isa_hot.py), and the depth-lane sums could not be accumulated in place (composite_group).
+      if constexpr (!NANCHK && !SLAB && !BIG && (K == 2 || K == 4)) {
+        // The tame loop carries the two ray flags as the wave's lane masks, in SGPRs: `am` the rays
+        // that go on (all K lanes of a ray alike), `mm` the lanes whose sample exists.  A flag kept per
+        // lane across the iterations lives as 0 / 1 in a VGPR and is converted to a mask and back around
+        // every use (11 VALU per lit iteration); as masks the flags cost SALU only: the body's
+        // execution mask is `am` itself, the lanes that sample are `mm`, the exit tests' compare
+        // results are taken as they come (ballot), and "any lane of the group" is shifts and masks of
+        // the 64-bit word (group_or_mask).  Same flags, same order of every test: a lane outside `am`
+        // -- a finished or a parked ray -- executes nothing, as with `continue`.
+        const uint64_t am0 = __ballot(R.alive), mine0 = __ballot(R.mine);
+        uint64_t am = am0, mm = am0 & mine0;
+        for (int k = 0, Su = __builtin_amdgcn_readfirstlane(S); k < Su && am != 0ull; k += K) {
+          if (__builtin_amdgcn_inverse_ballot_w64(am)) {
+            float r = 0.f, gg = 0.f, b = 0.f, alpha = 0.f;
+            bool shaded = false;
+            if (__builtin_amdgcn_inverse_ballot_w64(mm))
+              sample_at<MODE, AB_ALIAS, SHARE2, BIG, NANCHK, NL, WC>(P, L, B, staged, WC || (!VR_WHOLE_SPLIT && whole),
+                                                                 R.pos, R.o, r, gg, b, alpha, shaded, rv, pre);
+            if (COUNT) {
+              ++C.iter;
+              C.lit += (MODE != 0 && __any(shaded)) ? 1u : 0u;
+            }
+            // (the flags these two leave are the tests below, taken on every lane at once)
+            bool go = true, mine = true;
+            composite_group<K, 0, VR_ZERO_FILL>(P, R, go, 1.f, r, gg, b, alpha, thr);
+            advance_k<K>(P, mine, R.nsteps, R.t, R.tfar, R.pos, R.step, cap);  // to sample + K
+          }
+          // advance_k's exit test and the opacity exit (a ray that stopped at one sample of the group
+          // composited no further one, so its sum.a is still the one that exceeded thr), outside the
+          // body: the compares' results are the masks (a lane outside `am` tests its old state, and is
+          // masked)
+          mm &= am & __ballot(R.nsteps < cap) & __ballot(!(R.t > R.tfar));
+          am &= __ballot(!(R.sa > thr)) & group_or_mask<K>(mm);
+        }
+        // (a lane that was not alive on entry -- a parked ray among them -- keeps its `mine`)
+        R.alive = __builtin_amdgcn_inverse_ballot_w64(am);
+        R.mine = __builtin_amdgcn_inverse_ballot_w64(mm | (mine0 & ~am0));
+      } else
       for (int k = 0, Su = __builtin_amdgcn_readfirstlane(S); k < Su; k += K) {
         if (!__any(R.alive)) break;
         if (!R.alive) continue;
@@ -799,14 +879,14 @@ __device__ __forceinline__ void march(const RenderParams &P, float *L, int lane,
         }
         bool shaded = false;
         if (take) {
-          sample_at<MODE, AB_ALIAS, SHARE2, BIG, NANCHK, NL>(P, L, B, staged, WC || (!VR_WHOLE_SPLIT && whole), R.pos,
-                                                         R.o, r, gg, b, alpha, shaded, rv, pre);
+          sample_at<MODE, AB_ALIAS, SHARE2, BIG, NANCHK, NL, WC>(P, L, B, staged, WC || (!VR_WHOLE_SPLIT && whole),
+                                                             R.pos, R.o, r, gg, b, alpha, shaded, rv, pre);
         }
         if (COUNT) {
           ++C.iter;
           C.lit += (MODE != 0 && __any(shaded)) ? 1u : 0u;
         }
-        composite_group<K, 0, VR_ZERO_FILL && !NANCHK && !SLAB>(P, R, ex ? 1.f : 0.f, r, gg, b, alpha, thr);
+        composite_group<K, 0, VR_ZERO_FILL && !NANCHK && !SLAB>(P, R, R.alive, ex ? 1.f : 0.f, r, gg, b, alpha, thr);
         if (SLAB && !inside) {
           if (R.alive && group_any<K>(R.mine && !ex)) {  // left the slab still unfinished
             // the next slab resumes at the group's first sample beyond this one (samples of a
@@ -913,7 +993,9 @@ template <int K, int MODE, bool AB_ALIAS, bool COUNT, bool SHARE2, bool BIG, int
 __global__ __launch_bounds__(64 * VR_WG_WAVES, march_min_eu(CAP, SCHED)) void march_kernel(const RenderParams P) {
   using TS = TileShape<K>;
   __shared__ float lds[VR_WG_WAVES][CAP];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // (the wave index as a scalar: the slot's base address then is one, and the sample loop folds it
+  // into its per-chunk address constant in SALU, sample_at FOLD)
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float *L = lds[wave];
   constexpr bool ORDERED = SCHED >= 1 && SCHED <= 3;
   constexpr bool TIMED = SCHED == 1 || SCHED == 2;  // SCHED 3: the order only

@@ -261,25 +261,33 @@ __device__ __forceinline__ float lerp_zrows(const f4a8 &r0, const f4a8 &r1, cons
   const float c0 = lerp(c00, c10, ay.w), c1 = lerp(c01, c11, ay.w);
   return lerp(c0, c1, az.w);
 }
-__device__ __forceinline__ float fetch_small_z(const DevTex &t, const AxF &ax, const AxF &ay, const AxF &az) {
-  const uint32_t o = (uint32_t)fmaf(az.fl, t.fpxy4, fmaf(ay.fl, t.fpx4, fmaf(ax.fl, 4.f, t.fbase4)));
-  const uint32_t o2 = o + o, px8 = t.px * 8u;  // entries are 8 bytes
-  const char *b = reinterpret_cast<const char *>(t.zp);
+// The entries are 8 bytes, so the byte offset is formed with the doubled terms of the launch
+// (RenderParams::lutz_*: 8 px, 8 pxy, 8 (pxy + px + 1)) -- exact as fetch_small's: every partial sum is
+// an integer multiple of 8 below 2^25 -- and converted once, with no shift after it.  The row pitch
+// in bytes is a parameter of its own (lutz_px8) rather than lut.px * 8: a value that is a plain
+// kernel-argument load the compiler loads again where it is used, instead of holding the product in
+// an SGPR that spills to a VGPR lane across the sample loop (a v_readlane_b32 per sample).
+__device__ __forceinline__ uint32_t lutz_px8(const RenderParams &P) { return P.lutz_px8; }
+__device__ __forceinline__ float fetch_small_z(const RenderParams &P, const AxF &ax, const AxF &ay, const AxF &az) {
+  const uint32_t o2 =
+      (uint32_t)fmaf(az.fl, P.lutz_fpxy8, fmaf(ay.fl, P.lutz_fpx8, fmaf(ax.fl, 8.f, P.lutz_fbase8)));
+  const uint32_t px8 = lutz_px8(P);
+  const char *b = reinterpret_cast<const char *>(P.lut.zp);
   const f4a8 r0 = *reinterpret_cast<const f4a8 *>(b + o2);
   const f4a8 r1 = *reinterpret_cast<const f4a8 *>(b + (o2 + px8));
   return lerp_zrows(r0, r1, ax, ay, az);
 }
-__device__ __forceinline__ void fetch_small2_z(const DevTex &t, const AxF &ax, const AxF &ay0, const AxF &az0,
+__device__ __forceinline__ void fetch_small2_z(const RenderParams &P, const AxF &ax, const AxF &ay0, const AxF &az0,
                                                const AxF &ay1, const AxF &az1, float &v0, float &v1) {
-  const float ox = fmaf(ax.fl, 4.f, t.fbase4);
-  const uint32_t o0 = (uint32_t)fmaf(az0.fl, t.fpxy4, fmaf(ay0.fl, t.fpx4, ox));
-  const uint32_t o1 = (uint32_t)fmaf(az1.fl, t.fpxy4, fmaf(ay1.fl, t.fpx4, ox));
-  const uint32_t px8 = t.px * 8u;
-  const char *b = reinterpret_cast<const char *>(t.zp);
-  const f4a8 a0 = *reinterpret_cast<const f4a8 *>(b + (o0 + o0));
-  const f4a8 a1 = *reinterpret_cast<const f4a8 *>(b + (o0 + o0 + px8));
-  const f4a8 b0 = *reinterpret_cast<const f4a8 *>(b + (o1 + o1));
-  const f4a8 b1 = *reinterpret_cast<const f4a8 *>(b + (o1 + o1 + px8));
+  const float ox = fmaf(ax.fl, 8.f, P.lutz_fbase8);
+  const uint32_t o0 = (uint32_t)fmaf(az0.fl, P.lutz_fpxy8, fmaf(ay0.fl, P.lutz_fpx8, ox));
+  const uint32_t o1 = (uint32_t)fmaf(az1.fl, P.lutz_fpxy8, fmaf(ay1.fl, P.lutz_fpx8, ox));
+  const uint32_t px8 = lutz_px8(P);
+  const char *b = reinterpret_cast<const char *>(P.lut.zp);
+  const f4a8 a0 = *reinterpret_cast<const f4a8 *>(b + o0);
+  const f4a8 a1 = *reinterpret_cast<const f4a8 *>(b + (o0 + px8));
+  const f4a8 b0 = *reinterpret_cast<const f4a8 *>(b + o1);
+  const f4a8 b1 = *reinterpret_cast<const f4a8 *>(b + (o1 + px8));
   v0 = lerp_zrows(a0, a1, ax, ay0, az0);
   v1 = lerp_zrows(b0, b1, ax, ay1, az1);
 }
@@ -580,11 +588,31 @@ __device__ __forceinline__ float acospi_q(float q);
 #ifndef VR_FAST_CLAMP
 #define VR_FAST_CLAMP 1
 #endif
-__device__ __forceinline__ float acospi_f(float q) {
+// The leading coefficient of acospi_q's polynomial in a VGPR, for a caller that takes several angles
+// (shade_fast: one v_mov_b32 per shaded sample instead of one per angle).  `dep`, a value of the
+// sample, is an operand the move does not read: with it the compiler cannot hoist the constant out
+// of the sample loop, where it would hold a register across it (16 B of scratch at the 96-VGPR cap).
+__device__ __forceinline__ float acospi_c0(float dep) {
+  float c;
+  asm("v_mov_b32 %0, 0x3967ab32" : "=v"(c) : "v"(dep));
+  return c;
+}
+__device__ __forceinline__ float acospi_q(float q, float c0);
+__device__ __forceinline__ float acospi_f(float q, float c0) {
   if (VR_FAST_CLAMP == 2) q = q < -1.f ? -1.f : q;  // (the explicit form: a compare and a select)
-  return acospi_q(q);
+  return acospi_q(q, c0);
 }
 __device__ __forceinline__ float acospi_q(float q) {
+#if VR_FAST_ACOS && VR_ACOS_LITERALS
+  float c0;
+  asm("v_mov_b32 %0, 0x3967ab32" : "=v"(c0));
+  return acospi_q(q, c0);
+#else
+  return acospi_q(q, 2.209365193e-04f);
+#endif
+}
+// c0: the polynomial's leading coefficient 0x3967ab32 (acospi_c0)
+__device__ __forceinline__ float acospi_q(float q, float c0) {
 #if VR_ABLATE & 2
   return fmaf(q, -0.5f, 0.5f);  // diagnostic: the angle's cost removed (wrong image)
 #endif
@@ -596,8 +624,7 @@ __device__ __forceinline__ float acospi_q(float q) {
   // coefficients in SGPRs across the sample loop -- where they push other values into v_readlane
   // spills.  Same single rounding per step (d = s0 * s1 + K).
   float p;
-  asm("v_mov_b32 %0, 0x3967ab32\n\t"
-      "v_fmaak_f32 %0, %0, %1, 0xbaa77072\n\t"
+  asm("v_fmaak_f32 %0, %2, %1, 0xbaa77072\n\t"
       "v_fmaak_f32 %0, %0, %1, 0x3b67639e\n\t"
       "v_fmaak_f32 %0, %0, %1, 0xbbd8c4b8\n\t"
       "v_fmaak_f32 %0, %0, %1, 0x3c2a004e\n\t"
@@ -606,9 +633,9 @@ __device__ __forceinline__ float acospi_q(float q) {
       "v_fmaak_f32 %0, %0, %1, 0xbd8be5f3\n\t"
       "v_fmaak_f32 %0, %0, %1, 0x3f000000"
       : "=&v"(p)
-      : "v"(t));
+      : "v"(t), "v"(c0));
 #else
-  float p = 2.209365193e-04f;
+  float p = c0;
   p = fmaf(p, t, -1.277460018e-03f);
   p = fmaf(p, t, 3.530717921e-03f);
   p = fmaf(p, t, -6.615247577e-03f);
@@ -715,6 +742,13 @@ __device__ __forceinline__ void shade_fast(const RenderParams &P, const f3 g, co
                                           const DevLight *pre = nullptr) {
   static_assert(NL == 0 || ((NL == 1 || NL == 2) && TAME), "specialised for hoisted lights only");
   const int nl = NL ? NL : P.num_lights;
+  // the sample's angles (1 + 2 per light) share the polynomial's leading coefficient: one move here
+#if VR_FAST_ACOS && VR_ACOS_LITERALS
+  const float c0 = acospi_c0(g.x);
+#else
+  const float c0 = 2.209365193e-04f;
+#endif
+  auto ang = [&](float q) { return acospi_f(q, c0); };
   // n = -g * rsq(g.g): rsq(0) = inf gives the reference's NaN normal for a zero gradient
   float ginv;
   if constexpr (XN) ginv = rcp_sqrt_cr(dot3(g, g));  // the oracle's 1 / sqrtf(g.g), bit for bit
@@ -758,7 +792,7 @@ __device__ __forceinline__ void shade_fast(const RenderParams &P, const f3 g, co
     return q;
   };
   if constexpr (NEED) need = lip2 < VR_HYB_TA * li2;
-  const float alpha_n = acospi_f(dot3(n, li) * (rn * rsq_c(li2)));
+  const float alpha_n = ang(dot3(n, li) * (rn * rsq_c(li2)));
   const AxF la = axis_lut<true, TAME>(alpha_n, P.lut.fnx);
   int i = 0;
   if (TAME || (P.lut.p != nullptr && P.lut.small && !P.lut.one)) {
@@ -773,17 +807,17 @@ __device__ __forceinline__ void shade_fast(const RenderParams &P, const f3 g, co
       const float dlo0 = dot3(lo0, n), dlo1 = dot3(lo1, n);
       const f3 lop0 = mk(fmaf(-dlo0, n.x, lo0.x), fmaf(-dlo0, n.y, lo0.y), fmaf(-dlo0, n.z, lo0.z));
       const f3 lop1 = mk(fmaf(-dlo1, n.x, lo1.x), fmaf(-dlo1, n.y, lo1.y), fmaf(-dlo1, n.z, lo1.z));
-      const float beta0 = acospi_f(dlo0 * (rn * rsq_c(dot3(lo0, lo0))));
-      const float gamma0 = acospi_f(gamma_q(lo0, lop0));
-      const float beta1 = acospi_f(dlo1 * (rn * rsq_c(dot3(lo1, lo1))));
-      const float gamma1 = acospi_f(gamma_q(lo1, lop1));
+      const float beta0 = ang(dlo0 * (rn * rsq_c(dot3(lo0, lo0))));
+      const float gamma0 = ang(gamma_q(lo0, lop0));
+      const float beta1 = ang(dlo1 * (rn * rsq_c(dot3(lo1, lo1))));
+      const float gamma1 = ang(gamma_q(lo1, lop1));
       float light0, light1;
 #if VR_ABLATE & 1  // diagnostic: the LUT fetch's cost removed (wrong image)
       light0 = beta0 + gamma0 + la.w;
       light1 = beta1 + gamma1 + la.w;
 #else
       if (TAME && VR_LUT_ZPAIR)  // the host binds a tame launch's LUT with its z-paired copy
-        fetch_small2_z(P.lut, la, axis_lut<true, TAME>(beta0, P.lut.fny), axis_lut<true, TAME>(gamma0, P.lut.fnz),
+        fetch_small2_z(P, la, axis_lut<true, TAME>(beta0, P.lut.fny), axis_lut<true, TAME>(gamma0, P.lut.fnz),
                        axis_lut<true, TAME>(beta1, P.lut.fny), axis_lut<true, TAME>(gamma1, P.lut.fnz), light0, light1);
       else
         fetch_small2(P.lut, la, axis_lut<true, TAME>(beta0, P.lut.fny), axis_lut<true, TAME>(gamma0, P.lut.fnz),
@@ -806,10 +840,10 @@ __device__ __forceinline__ void shade_fast(const RenderParams &P, const f3 g, co
     const float dlo0 = dot3(lo0, n), dlo1 = dot3(lo1, n);
     const f3 lop0 = mk(fmaf(-dlo0, n.x, lo0.x), fmaf(-dlo0, n.y, lo0.y), fmaf(-dlo0, n.z, lo0.z));
     const f3 lop1 = mk(fmaf(-dlo1, n.x, lo1.x), fmaf(-dlo1, n.y, lo1.y), fmaf(-dlo1, n.z, lo1.z));
-    const float beta0 = acospi_f(dlo0 * (rn * rsq_c(dot3(lo0, lo0))));
-    const float gamma0 = acospi_f(gamma_q(lo0, lop0));
-    const float beta1 = acospi_f(dlo1 * (rn * rsq_c(dot3(lo1, lo1))));
-    const float gamma1 = acospi_f(gamma_q(lo1, lop1));
+    const float beta0 = ang(dlo0 * (rn * rsq_c(dot3(lo0, lo0))));
+    const float gamma0 = ang(gamma_q(lo0, lop0));
+    const float beta1 = ang(dlo1 * (rn * rsq_c(dot3(lo1, lo1))));
+    const float gamma1 = ang(gamma_q(lo1, lop1));
     const float light0 = lut_light<true>(P.lut, la, beta0, gamma0);
     const float light1 = lut_light<true>(P.lut, la, beta1, gamma1);
     const float rl0 = refl * light0;
@@ -826,9 +860,9 @@ __device__ __forceinline__ void shade_fast(const RenderParams &P, const f3 g, co
     const f3 lo = mk(L.px - pos.x, L.py - pos.y, L.pz - pos.z);
     const float dlo = dot3(lo, n);
     const f3 lop = mk(fmaf(-dlo, n.x, lo.x), fmaf(-dlo, n.y, lo.y), fmaf(-dlo, n.z, lo.z));
-    const float beta = acospi_f(dlo * (rn * rsq_c(dot3(lo, lo))));
-    const float gamma = acospi_f(gamma_q(lo, lop));
-    const float rl = refl * (TAME ? (VR_LUT_ZPAIR ? fetch_small_z(P.lut, la, axis_lut<true, TAME>(beta, P.lut.fny),
+    const float beta = ang(dlo * (rn * rsq_c(dot3(lo, lo))));
+    const float gamma = ang(gamma_q(lo, lop));
+    const float rl = refl * (TAME ? (VR_LUT_ZPAIR ? fetch_small_z(P, la, axis_lut<true, TAME>(beta, P.lut.fny),
                                                                  axis_lut<true, TAME>(gamma, P.lut.fnz))
                                                   : fetch_small(P.lut, la, axis_lut<true, TAME>(beta, P.lut.fny),
                                                                 axis_lut<true, TAME>(gamma, P.lut.fnz)))

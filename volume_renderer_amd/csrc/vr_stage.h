@@ -131,19 +131,41 @@ __device__ __forceinline__ float lds_tri(const float *L, const Box &B, int a, fl
 struct Cell {
   float c00, c10, c01, c11, c0, c1;
 };
-__device__ __forceinline__ float lds_tri_cell(const float *L, const Box &B, int a, float wx, float wy, float wz,
-                                              Cell &C) {
-  C.c00 = lerp(L[a], L[a + 1], wx);
-  C.c10 = lerp(L[a + B.px], L[a + B.px + 1], wx);
-  C.c01 = lerp(L[a + B.pxy], L[a + B.pxy + 1], wx);
-  C.c11 = lerp(L[a + B.pxy + B.px], L[a + B.pxy + B.px + 1], wx);
+// A cell of the slot by its LDS byte address (the slot is the wave's own LDS: vr_march.hip), and the
+// float `byte` bytes from it.
+typedef const __attribute__((address_space(3))) char *lds_cptr;
+__device__ __forceinline__ uint32_t lds_addr(const float *L) {
+  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) float *)L;
+}
+__device__ __forceinline__ lds_cptr lds_cell(const float *L, int a) {
+  return (lds_cptr)((const __attribute__((address_space(3))) float *)L + a);
+}
+__device__ __forceinline__ float lds_f(lds_cptr c, int byte) {
+  return *reinterpret_cast<const __attribute__((address_space(3))) float *>(c + byte);
+}
+// c: the cell whose (x, y, z) = (0, 0, 0) corner it points to.
+__device__ __forceinline__ float lds_tri_cell(lds_cptr c, const Box &B, float wx, float wy, float wz, Cell &C) {
+  const int px4 = B.px * 4, pxy4 = B.pxy * 4;
+  C.c00 = lerp(lds_f(c, 0), lds_f(c, 4), wx);
+  C.c10 = lerp(lds_f(c, px4), lds_f(c, px4 + 4), wx);
+  C.c01 = lerp(lds_f(c, pxy4), lds_f(c, pxy4 + 4), wx);
+  C.c11 = lerp(lds_f(c, pxy4 + px4), lds_f(c, pxy4 + px4 + 4), wx);
   C.c0 = lerp(C.c00, C.c10, wy);
   C.c1 = lerp(C.c01, C.c11, wy);
   return lerp(C.c0, C.c1, wz);
 }
 
+// The extra row (plane) of a y (z) tap pair relative to the centre's: +2 or -1.  Opaque, so that the
+// compiler multiplies it by the pitch (one v_mad_i32_i24 onto the address) instead of selecting
+// between two products, which on gfx950 costs two moves of SGPRs next to the select.
+__device__ __forceinline__ int tap_row(bool hi) {
+  int j = hi ? 2 : -1;
+  asm("" : "+v"(j));
+  return j;
+}
+
 // The six half-texel gradient taps of the fast variant (vr_sampling.h half_taps) from the slot, for
-// a sample whose centre cell (slot word ac, partial sums C, weights wx wy wz) and tap cells all lie
+// a sample whose centre cell (at cc, partial sums C, weights wx wy wz) and tap cells all lie
 // in the staged box.  Each tap is the trilinear fetch fetch_at would take -- same voxels, same
 // weights, the same lerps in the same order (x, then y, then z) -- but what two taps or a tap and
 // the centre compute alike is computed once: the x taps read their three voxels per row (the minus
@@ -151,17 +173,24 @@ __device__ __forceinline__ float lds_tri_cell(const float *L, const Box &B, int 
 // except one extra row pair; the z taps' xy-interpolated planes are the centre's c0, c1 except one
 // extra plane.  20 voxels and 27 lerps instead of 48 voxels and 42 lerps, with no per-tap box
 // test.  Returns the unhalved differences (plus - minus) per axis.
-__device__ __forceinline__ f3 half_grad_lds(const float *L, const Box &B, int ac, const AxS &sx, const AxS &sy,
-                                            const AxS &sz, float wx, float wy, float wz, const Cell &C) {
+__device__ __forceinline__ f3 half_grad_lds(lds_cptr cc, const Box &B, const AxS &sx, const AxS &sy, const AxS &sz,
+                                            float wx, float wy, float wz, const Cell &C) {
   f3 g;
+  // The per-lane choice of the extra voxel column, row and plane is made on byte addresses: for x a
+  // select between the inline constants 0 and -4; for y and z a select between the inline constants
+  // 2 and -1 (tap_row) and one 24-bit multiply-add of it by the chunk-uniform byte pitch (premultiplied
+  // in SALU; |2 pitch| is far below 2^23).  The slot words of centre word ac + (hi ? 0 : -1),
+  // ac + (hi ? 2 px : -px) and ac + (hi ? 2 pxy : -pxy).
+  auto at = [&](lds_cptr c, int byte) { return lds_f(c, byte); };
+  const int px4 = B.px * 4, pxy4 = B.pxy * 4;
   {  // x: cells a - 1 (minus) and a (plus), a = i + hi; three voxels per (y, z) row from a - 1
     const float tx = sx.w + (sx.hi ? -0.5f : 0.5f);
-    const int w = ac + (sx.hi ? 0 : -1);
+    const lds_cptr w = cc + (sx.hi ? 0 : -4);
     float m[4], p[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int o = w + ((r & 1) ? B.px : 0) + ((r & 2) ? B.pxy : 0);
-      const float x0 = L[o], x1 = L[o + 1], x2 = L[o + 2];
+      const int o = ((r & 1) ? px4 : 0) + ((r & 2) ? pxy4 : 0);
+      const float x0 = at(w, o), x1 = at(w, o + 4), x2 = at(w, o + 8);
       m[r] = lerp(x0, x1, tx);
       p[r] = lerp(x1, x2, tx);
     }
@@ -171,8 +200,8 @@ __device__ __forceinline__ f3 half_grad_lds(const float *L, const Box &B, int ac
   }
   {  // y: rows b - 1, b, b + 1 (b = j + hi) of the x-interpolated values; one row pair is new
     const float ty = sy.w + (sy.hi ? -0.5f : 0.5f);
-    const int w = ac + (sy.hi ? 2 * B.px : -B.px);
-    const float e0 = lerp(L[w], L[w + 1], wx), e1 = lerp(L[w + B.pxy], L[w + B.pxy + 1], wx);
+    const lds_cptr w = cc + __mul24(tap_row(sy.hi), px4);
+    const float e0 = lerp(at(w, 0), at(w, 4), wx), e1 = lerp(at(w, pxy4), at(w, pxy4 + 4), wx);
     const float y00 = sy.hi ? C.c00 : e0, y01 = sy.hi ? C.c10 : C.c00, y02 = sy.hi ? e0 : C.c10;  // z
     const float y10 = sy.hi ? C.c01 : e1, y11 = sy.hi ? C.c11 : C.c01, y12 = sy.hi ? e1 : C.c11;  // z + 1
     const float gm = lerp(lerp(y00, y01, ty), lerp(y10, y11, ty), wz);
@@ -181,8 +210,8 @@ __device__ __forceinline__ f3 half_grad_lds(const float *L, const Box &B, int ac
   }
   {  // z: planes c - 1, c, c + 1 (c = k + hi) of the xy-interpolated values; one plane is new
     const float tz = sz.w + (sz.hi ? -0.5f : 0.5f);
-    const int w = ac + (sz.hi ? 2 * B.pxy : -B.pxy);
-    const float q0 = lerp(L[w], L[w + 1], wx), q1 = lerp(L[w + B.px], L[w + B.px + 1], wx);
+    const lds_cptr w = cc + __mul24(tap_row(sz.hi), pxy4);
+    const float q0 = lerp(at(w, 0), at(w, 4), wx), q1 = lerp(at(w, px4), at(w, px4 + 4), wx);
     const float pe = lerp(q0, q1, wy);
     const float z0 = sz.hi ? C.c0 : pe, z1 = sz.hi ? C.c1 : C.c0, z2 = sz.hi ? pe : C.c1;
     g.z = lerp(z1, z2, tz) - lerp(z0, z1, tz);
