@@ -374,6 +374,64 @@ int vr_render_transfer_device(vr_context *h, const vr_render_args *args, const v
                               const vr_partition *part, float *d_out, float *d_alpha /* may be NULL */,
                               unsigned long long *d_steps /* 2 counters, may be NULL */, void *stream);
 
+/* --- clip planes: cut-away views for the single-handle render calls (no reference counterpart) ---
+ * A geometric cut-away: no volume data changes, each ray's interval [tnear, tfar] is shortened.
+ * Coordinates.  A plane keeps the half-space normal . q + offset >= 0 of the normalized volume
+ * coordinate q in the dimension order of Data: q_j runs from 0 to 1 across dimension j (dims[j]) of the
+ * emission volume, the centre of voxel i (0-based) at (i + 0.5) / d_j.  q is the sampler's own
+ * coordinate (pos - bmin) * bscale; normal[j] pairs with dims[j] -- the axis order that
+ * element_size_um, the light positions and the rotation matrix have reversed (element_size_um[2 - j]
+ * belongs to dims[j]).  The kept region is the intersection of the planes and of the box.
+ * State.  The planes are state of the handle: vr_set_clip replaces the set (n = 0 clears it, planes may
+ * then be NULL), vr_delete drops it with the handle.  vr_get_clip writes the n planes as they were set
+ * into planes[0 .. n-1] (room for VR_CLIP_MAX) and their count into *n.
+ * Errors of vr_set_clip, checked before the handle (they need no device), each VR_ERR_ARGUMENT: n
+ * outside 0..VR_CLIP_MAX; planes NULL with n > 0; a non-finite normal component or offset; an all-zero
+ * normal.  vr_get_clip: planes or n NULL is VR_ERR_ARGUMENT.
+ * Host conversion, once per launch, in fp32, every operation rounded once.  With bmin_k and bscale_k
+ * the box of the frame (k the kernel axis = the dimension of Data) and n_k = normal[k]:
+ *   N_k = n_k * bscale_k;
+ *   D   = fmaf(-N_2, bmin_2, fmaf(-N_1, bmin_1, fmaf(-N_0, bmin_0, offset))).
+ * Per ray.  After the ray set-up of 'render' has produced the origin o, the direction d, the box hit
+ * and tnear (clamped to 0) and tfar, the planes are applied in the order they were set:
+ *   s0 = fmaf(N_2, o_2, fmaf(N_1, o_1, fmaf(N_0, o_0, D)));
+ *   sd = fmaf(N_2, d_2, fmaf(N_1, d_1, N_0 * d_0));
+ *   tc = (-s0) / sd                                   (one IEEE division);
+ *   sd > 0:  if (tc > tnear) tnear = tc;    sd < 0:  if (tc < tfar) tfar = tc;
+ *   sd == +-0 or NaN: the ray is a miss unless s0 >= 0.
+ * After the last plane the ray is a hit only if it hit the box and tnear <= tfar (a NaN fails).  A hit
+ * ray runs exactly as without planes from the new tnear: pos_0 = fmaf(d, tnear, o), t_0 = tnear, the
+ * unchanged recurrences, the cap and the exit tests against the new tfar; a miss writes each render's
+ * miss values.  Clipping acts on sample positions only: the gradient taps, the reflection and LUT
+ * fetches and the isosurface's bisection read the unclipped volume.  The isosurface's rule that a hit
+ * at sample 0 is the surface point itself gives a cut object a capped cut face, its depth the clipped
+ * tnear.
+ * Which calls honour the planes.
+ *   vr_render_projection[_device], vr_render_isosurface[_device], vr_render_transfer[_device]: clipped
+ *     instantiations of their kernels, the empty-space leap left on; partition and d_steps as without.
+ *   vr_render, vr_render_device: the general one-lane kernel (not the LDS-staged march) in a clipped
+ *     instantiation, with the handle's shading variant (fast; exact under VR_EXACT_SHADE=1); partition
+ *     and d_steps[0..1] as without.  Much slower than the march (about seven times on a whole
+ *     frame; less the more is cut away): DESIGN.md s13.
+ *   vr_render_stereo[_device]: the two clipped renders with props[0] = -base and +base, bit for bit.
+ *   vr_render_channels[_device] (any channel's handle), vr_render_slab and every render call on a
+ *     multi-device group handle: VR_ERR_UNSUPPORTED, the message names the clip planes.
+ * With no planes set every call launches the kernels it launches without this feature, and
+ * vr_last_march_kernel reports what it did. */
+#define VR_CLIP_MAX 6 /* enough for a crop box */
+typedef struct vr_clip_plane {
+  float normal[3]; /* pairs with dims[0..2] of Data */
+  float offset;
+} vr_clip_plane;
+int vr_set_clip(vr_context *h, const vr_clip_plane *planes, int32_t n); /* n = 0 clears */
+int vr_get_clip(vr_context *h, vr_clip_plane *planes /* VR_CLIP_MAX */, int32_t *n);
+
+/* The host conversion above on the CPU (needs no device), for tests: out[i] = {N_0, N_1, N_2, D} of
+ * planes[i] for the box bmin[3], bscale[3].  The argument checks of vr_set_clip; a NULL bmin or
+ * bscale, or a NULL out with n > 0, is VR_ERR_ARGUMENT. */
+int vr_clip_convert_host(const vr_clip_plane *planes, int32_t n, const float bmin[3], const float bscale[3],
+                         float *out /* [n][4] */);
+
 /* The kernel's table lookup on the CPU (needs no device): out[k * m + j] = L(table plane k, n, lim,
  * c[j]) for the ncomp planes table[k * n + i].  VR_ERR_ARGUMENT for a NULL pointer with m > 0, an n
  * outside 2..VR_TF_MAX_ENTRIES, ncomp < 1, or limits that are not finite with lo < hi. */

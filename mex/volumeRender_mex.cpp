@@ -331,5 +331,32 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     if (nlhs > 1) plhs[1] = alpha; else mxDestroyArray(alpha);
     return;
   }
+  if (!strcmp(cmd, "set_clip")) {
+    // volumeRender('set_clip', h, planes) (vr_set_clip): planes single 4 x n, columns [n0; n1; n2; offset]
+    // keeping n . q + offset >= 0 of the normalized volume coordinate q (dimension order of Data);
+    // [] or false clears the set.  The planes stay with the handle until the next 'set_clip'.
+    if (nlhs > 0) mexErrMsgTxt("Too many output arguments.");
+    if (nrhs < 3) mexErrMsgTxt("insufficient parameter!");
+    if (nrhs > 3) mexErrMsgTxt("set_clip: too many input arguments");
+    const mxArray *pl = prhs[2];
+    if (mxIsClass(pl, "logical")) {
+      if (mxGetNumberOfElements(pl) != 1 || mxGetScalar(pl) != 0.0)
+        mexErrMsgTxt("set_clip: planes must be a single 4 x n matrix, [] or false");
+      check(vr_set_clip(h, nullptr, 0));
+      return;
+    }
+    if (mxGetNumberOfElements(pl) == 0) {
+      check(vr_set_clip(h, nullptr, 0));
+      return;
+    }
+    if (mxGetClassID(pl) != mxSINGLE_CLASS || mxIsComplex(pl) || mxGetNumberOfDimensions(pl) != 2 || mxGetM(pl) != 4)
+      mexErrMsgTxt("set_clip: planes must be a single 4 x n matrix, [] or false");
+    const mwSize n = mxGetN(pl);
+    if (n > 0x7fffffff) mexErrMsgTxt("set_clip: too many planes");
+    // a 4 x n single matrix is n vr_clip_plane records in memory (column-major)
+    static_assert(sizeof(vr_clip_plane) == 4 * sizeof(float), "vr_clip_plane is four floats");
+    check(vr_set_clip(h, static_cast<const vr_clip_plane *>(mxGetData(pl)), (int32_t)n));
+    return;
+  }
   mexErrMsgTxt(("Unknown command: " + std::string(cmd)).c_str());
 }

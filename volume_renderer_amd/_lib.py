@@ -24,6 +24,7 @@ VR_PROJ_MIP, VR_PROJ_SUM = 0, 1
 # enum vr_transfer_coord, VR_TF_MAX_ENTRIES
 VR_TF_VALUE, VR_TF_DEPTH = 0, 1
 VR_TF_MAX_ENTRIES = 1024
+VR_CLIP_MAX = 6
 
 
 class VrVolume(ctypes.Structure):
@@ -57,6 +58,10 @@ class VrTransfer(ctypes.Structure):
     _fields_ = [("colormap", c_void_p), ("n_color", c_int32), ("clim", c_float * 2),
                 ("alphamap", c_void_p), ("n_alpha", c_int32), ("alim", c_float * 2),
                 ("coord", c_int32), ("reserved", c_int32)]
+
+
+class VrClipPlane(ctypes.Structure):
+    _fields_ = [("normal", c_float * 3), ("offset", c_float)]
 
 
 class VrChannel(ctypes.Structure):
@@ -107,6 +112,9 @@ SIGNATURES = [
     ("vr_render_transfer_device", c_int, [c_void_p, POINTER(VrRenderArgs), POINTER(VrTransfer), POINTER(VrPartition),
                                           c_void_p, c_void_p, c_void_p, c_void_p]),
     ("vr_transfer_lookup_host", c_int, [c_void_p, c_int32, c_int32, POINTER(c_float), c_void_p, c_uint64, c_void_p]),
+    ("vr_set_clip", c_int, [c_void_p, POINTER(VrClipPlane), c_int32]),
+    ("vr_get_clip", c_int, [c_void_p, POINTER(VrClipPlane), POINTER(c_int32)]),
+    ("vr_clip_convert_host", c_int, [POINTER(VrClipPlane), c_int32, POINTER(c_float), POINTER(c_float), c_void_p]),
     ("vr_partition_columns", c_int64, [c_int64, POINTER(VrPartition)]),
     ("vr_assemble_partitions", c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int64, c_void_p,
                                        c_void_p]),

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/vrhip.h"
+#include "vr_clip.h"
 #include "vr_device.h"
 #include "vr_resources.h"
 #include "vr_transfer.h"
@@ -48,16 +49,19 @@
 int exact_lanes(int K, bool fast) { return (fast || VR_WITH_K8) ? K : std::min(K, 2); }
 
 namespace vr {
-hipError_t launch_render(const RenderParams &P, int mode, bool ab_alias, bool big, bool share, hipStream_t s);
+// clip (here and below): the launch's plane set (vr_clip.h), or null / n == 0 -- the unclipped kernels
+hipError_t launch_render(const RenderParams &P, int mode, bool ab_alias, bool big, bool share, hipStream_t s,
+                         const ClipSet *clip);
 // vr_project.hip: mode = vr_projection; aux: the [plane_cols][H] aux plane or null
-hipError_t launch_project(const RenderParams &P, int mode, float *aux, bool big, bool probe, hipStream_t s);
+hipError_t launch_project(const RenderParams &P, int mode, float *aux, bool big, bool probe, hipStream_t s,
+                          const ClipSet *clip);
 hipError_t launch_isosurface(const RenderParams &P, int grad, float level, float *depth, float *normal, bool big,
-                             bool probe, hipStream_t s);
+                             bool probe, hipStream_t s, const ClipSet *clip);
 // vr_transfer.hip: tab = the segment records of transfer_table_units(nc, na) 16-byte units
 uint32_t transfer_table_units(int32_t nc, int32_t na);
 hipError_t launch_transfer(const RenderParams &P, int grad, const float *tab, int32_t nc, int32_t na, float clo,
                            float cinv, float alo, float ainv, int32_t coord, bool ab_alias, float *alpha, bool big,
-                           bool probe, hipStream_t s);
+                           bool probe, hipStream_t s, const ClipSet *clip);
 // vr_march.hip built with VR_MARCH_FAST=1 / 0 (namespaces fast / exact) and VR_MARCH_K = 1, 2, 4, 8
 #define VR_DECL_MARCH(ns)                                                                                 \
   namespace ns {                                                                                         \
@@ -346,6 +350,9 @@ struct vr_context {
   // do_render / a fused channel launch), reported by mem_info; created on first use
   hipEvent_t tev[2] = {nullptr, nullptr};
   bool timed = false;
+  // clip planes (vr_set_clip), as the caller gave them; converted per launch (clip_set)
+  vr_clip_plane clip[VR_CLIP_MAX] = {};
+  int32_t nclip = 0;
 };
 
 namespace {
@@ -731,6 +738,41 @@ struct Frame {
   vr_context::Schedule *sched = nullptr;       // the launch shape's schedule (attach_schedule)
 };
 
+
+// The argument checks of vr_set_clip (include/vrhip.h): before the handle, no device needed.
+int check_clip(const vr_clip_plane *planes, int32_t n) {
+  if (n < 0 || n > VR_CLIP_MAX) return fail(VR_ERR_ARGUMENT, "clip planes: 0 .. " + std::to_string(VR_CLIP_MAX) + " planes");
+  if (n > 0 && !planes) return fail(VR_ERR_ARGUMENT, "clip planes: planes is NULL");
+  for (int32_t i = 0; i < n; ++i) {
+    const vr_clip_plane &p = planes[i];
+    if (!std::isfinite(p.normal[0]) || !std::isfinite(p.normal[1]) || !std::isfinite(p.normal[2]) ||
+        !std::isfinite(p.offset))
+      return fail(VR_ERR_ARGUMENT, "clip planes: non-finite plane");
+    if (p.normal[0] == 0.f && p.normal[1] == 0.f && p.normal[2] == 0.f)
+      return fail(VR_ERR_ARGUMENT, "clip planes: all-zero normal");
+  }
+  return VR_OK;
+}
+
+// The host conversion of the header: the plane normal . q + offset >= 0 of q = (p - bmin) * bscale as
+// N . p + D >= 0 of the world position p, in fp32 (-ffp-contract=off: every operation rounded once).
+void convert_clip(const vr_clip_plane &p, const float bmin[3], const float bscale[3], float out[4]) {
+  for (int k = 0; k < 3; ++k) out[k] = p.normal[k] * bscale[k];
+  out[3] = fmaf(-out[2], bmin[2], fmaf(-out[1], bmin[1], fmaf(-out[0], bmin[0], p.offset)));
+}
+
+// The plane set of a launch of frame P on handle h (n == 0: none, the unclipped kernels).
+vr::ClipSet clip_set(const vr_context *h, const vr::RenderParams &P) {
+  vr::ClipSet C{};
+  C.n = h->nclip;
+  for (int32_t i = 0; i < h->nclip; ++i) convert_clip(h->clip[i], P.bmin, P.bscale, C.pl[i]);
+  return C;
+}
+
+int clip_unsupported(const char *what) {
+  return fail(VR_ERR_UNSUPPORTED, std::string(what) + ": clip planes are set on the handle (vr_set_clip); they are "
+                                                      "honoured by the single-handle render calls only");
+}
 
 // Per-sample bound of the drift between a predicted position fma(step, k, pos) and k sequentially
 // rounded additions, in emission texels per axis: |pos| <= |box| + |eye| (fp32 rounding 1.2e-7 per
@@ -1417,7 +1459,9 @@ int do_render(vr_context *h, const vr_render_args *a, const vr_partition *part, 
   // LDS-staged march (vr_march.hip) whenever the emission texture is a real grid and, for the
   // on-the-fly gradient, is also the gradient texture; the plain kernel covers everything else.
   // Both produce bit-identical images (tests/test_gpu_parity.py::test_kernel_variants...).
-  const bool march = P.em.p && !P.em.one && (F.mode != 1 || F.share) && !test_flag("VR_NO_LDS");
+  // Clip planes (vr_set_clip) go through the general kernel: the staged march knows nothing of them.
+  const vr::ClipSet clip = clip_set(h, P);
+  const bool march = P.em.p && !P.em.one && (F.mode != 1 || F.share) && !test_flag("VR_NO_LDS") && clip.n == 0;
   P.gvec = nullptr;
   if (march && F.mode == 2 && F.share && !test_flag("VR_NO_GVEC")) {
     // interleave the three gradient textures (one 16-byte load per voxel instead of three 4-byte
@@ -1594,11 +1638,11 @@ int do_render(vr_context *h, const vr_render_args *a, const vr_partition *part, 
         }
     }
   } else {
-    VR_HIP(vr::launch_render(P, F.mode, F.ab_alias, F.big, F.share, stream));
+    VR_HIP(vr::launch_render(P, F.mode, F.ab_alias, F.big, F.share, stream, &clip));
     if (P.views > 1) {  // the general kernel renders one view per launch
       for (int i = 0; i < 3; ++i) P.eye[i] = P.eye2[i];
       P.out = P.out2;
-      VR_HIP(vr::launch_render(P, F.mode, F.ab_alias, F.big, F.share, stream));
+      VR_HIP(vr::launch_render(P, F.mode, F.ab_alias, F.big, F.share, stream, &clip));
     }
   }
   VR_HIP(L.finish());
@@ -1641,7 +1685,8 @@ int do_project(vr_context *h, const vr_render_args *a, int32_t mode, const vr_pa
   L.stream = stream;
   L.device = h->device;
   bind_reads(L);
-  VR_HIP(vr::launch_project(P, mode, d_aux, F.big, probe, stream));
+  const vr::ClipSet clip = clip_set(h, P);
+  VR_HIP(vr::launch_project(P, mode, d_aux, F.big, probe, stream, &clip));
   VR_HIP(L.finish());
   return VR_OK;
 }
@@ -1697,8 +1742,9 @@ int do_isosurface(vr_context *h, const vr_render_args *a, float level, const vr_
   L.device = h->device;
   bind_reads(L);
   stage_frame(L, P, g_tex.lights);
+  const vr::ClipSet clip = clip_set(h, P);
   VR_HIP(vr::launch_isosurface(P, g_tex.grad_method == G_LOOKUP ? 2 : 1, level, d_depth, d_normal, F.big, probe,
-                               stream));
+                               stream, &clip));
   VR_HIP(L.finish());
   return VR_OK;
 }
@@ -1858,9 +1904,10 @@ int do_transfer(vr_context *h, const vr_render_args *a, const vr_transfer *tf, c
     VR_HIP(L.stage(blob.data(), blob_bytes, &d_blob));
   }
   P.lights = reinterpret_cast<const vr::DevLight *>(static_cast<const char *>(d_blob) + tab_bytes);
+  const vr::ClipSet clip = clip_set(h, P);
   const hipError_t le = vr::launch_transfer(P, grad, static_cast<const float *>(d_blob), nc, na, tf->clim[0], cinv,
                                             na ? tf->alim[0] : 0.f, ainv, tf->coord, F.ab_alias, d_alpha, F.big, probe,
-                                            stream);
+                                            stream, &clip);
   if (ring) {  // the slot is free again when everything enqueued so far (its copy, the launch) completed
     vr_host::EventPtr ev;
     const hipError_t re = vr_host::record_event(stream, ev);
@@ -2668,6 +2715,7 @@ static int do_render_channels(const vr_channel *ch, int32_t n, int32_t stereo, f
   for (int i = 0; i < n; ++i) {
     if (!valid(ch[i].handle)) return fail(VR_ERR_HANDLE, "Handle not valid.");
     if (!ch[i].args) return fail(VR_ERR_ARGUMENT, "insufficient parameter!");
+    if (ch[i].handle->nclip) return clip_unsupported("vr_render_channels");
     for (int j = 0; j < i; ++j)
       if (ch[j].handle == ch[i].handle) return fail(VR_ERR_ARGUMENT, "channels need distinct handles");
     if (ch[i].args->resolution[0] != ch[0].args->resolution[0] || ch[i].args->resolution[1] != ch[0].args->resolution[1])
@@ -2832,6 +2880,7 @@ int vr_render(vr_context *h, const vr_render_args *a, float *out) {
     VR_HIP(hipMalloc(&h->d_out, bytes));
     h->d_out_bytes = bytes;
   }
+  if (!h->children.empty() && h->nclip) return clip_unsupported("vr_render on a multi-device group handle");
   Frame F;
   int rc = h->children.empty() ? do_render(h, a, nullptr, h->d_out, nullptr, nullptr, F)
                                : group_render(h, a, h->d_out, nullptr);
@@ -2850,6 +2899,7 @@ int vr_render_stereo(vr_context *h, const vr_render_args *a, float base, float *
   vr_host::prune_retired();  // buffers whose last launch has completed
   const size_t bytes = (size_t)a->resolution[0] * (size_t)a->resolution[1] * 3 * sizeof(float);
   if (bytes && (!out_left || !out_right)) return fail(VR_ERR_ARGUMENT, "output is NULL");
+  if (!h->children.empty() && h->nclip) return clip_unsupported("vr_render_stereo on a multi-device group handle");
   if (2 * bytes > h->d_out_bytes) {
     if (h->d_out) VR_HIP(hipFree(h->d_out));
     h->d_out = nullptr;
@@ -2909,6 +2959,7 @@ int vr_render_device(vr_context *h, const vr_render_args *a, const vr_partition 
   VR_GUARD_BEGIN
   DeviceGuard dg(h->device);
   vr_host::prune_retired();  // buffers whose last launch has completed
+  if (!h->children.empty() && h->nclip) return clip_unsupported("vr_render_device on a multi-device group handle");
   if (!h->children.empty() && !part && !d_steps) return group_render(h, a, d_out, (hipStream_t)stream);
   Frame F;
   return do_render(h, a, part, d_out, d_steps, (hipStream_t)stream, F);
@@ -3048,6 +3099,32 @@ int vr_render_transfer(vr_context *h, const vr_render_args *a, const vr_transfer
   VR_GUARD_END
 }
 
+int vr_set_clip(vr_context *h, const vr_clip_plane *planes, int32_t n) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (int rc = check_clip(planes, n)) return rc;
+  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
+  for (int32_t i = 0; i < n; ++i) h->clip[i] = planes[i];
+  h->nclip = n;
+  return VR_OK;
+}
+
+int vr_get_clip(vr_context *h, vr_clip_plane *planes, int32_t *n) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!planes || !n) return fail(VR_ERR_ARGUMENT, "clip planes: planes / n is NULL");
+  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
+  for (int32_t i = 0; i < h->nclip; ++i) planes[i] = h->clip[i];
+  *n = h->nclip;
+  return VR_OK;
+}
+
+int vr_clip_convert_host(const vr_clip_plane *planes, int32_t n, const float bmin[3], const float bscale[3],
+                         float *out) {
+  if (int rc = check_clip(planes, n)) return rc;
+  if (!bmin || !bscale || (n > 0 && !out)) return fail(VR_ERR_ARGUMENT, "clip planes: box / output is NULL");
+  for (int32_t i = 0; i < n; ++i) convert_clip(planes[i], bmin, bscale, out + 4 * (size_t)i);
+  return VR_OK;
+}
+
 int vr_transfer_lookup_host(const float *table, int32_t n, int32_t ncomp, const float lim[2], const float *c,
                             uint64_t m, float *out) {
   if (n < 2 || n > VR_TF_MAX_ENTRIES || ncomp < 1) return fail(VR_ERR_ARGUMENT, "table: 2 .. 1024 entries, ncomp >= 1");
@@ -3079,6 +3156,7 @@ int vr_render_slab(vr_context *h, const vr_render_args *a, const vr_slab *slab, 
   std::lock_guard<std::mutex> lk(g_mu);
   if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
   if (!a) return fail(VR_ERR_ARGUMENT, "insufficient parameter!");
+  if (h->nclip) return clip_unsupported("vr_render_slab");
   VR_GUARD_BEGIN
   DeviceGuard dg(h->device);
   vr_host::prune_retired();  // buffers whose last launch has completed

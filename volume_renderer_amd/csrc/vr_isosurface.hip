@@ -21,7 +21,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
+#include <type_traits>
 
+#include "vr_clip.h"
 #include "vr_device.h"
 #include "vr_sampling.h"
 #include "vr_stage.h"
@@ -49,12 +51,21 @@ struct IsoExtras {
   float *depth;
   float *normal;
 };
+// The same for a clipped instantiation, with the plane set (vr_clip.h).  The unclipped kernels keep
+// the arguments they had before there were planes.
+struct IsoExtrasClip : IsoExtras {
+  ClipSet clip;
+};
+template <bool CLIP>
+using IsoArgs = std::conditional_t<CLIP, IsoExtrasClip, IsoExtras>;
 
 // GRAD 1: on-the-fly gradient (six taps of the gem binding), 2: lookup (gx, gy, gz).
 // COUNT: steps[0] += search samples visited (leaped ones included), steps[1] += search samples
 // fetched, steps[2] += surface pixels.
-template <int GRAD, bool BIG, bool PROBE, bool COUNT>
-__global__ __launch_bounds__(256) void isosurface_kernel(const RenderParams P, const IsoExtras X) {
+// CLIP: the clip planes shorten [tnear, tfar] after ray_setup.  A hit at the first sample is then the
+// surface point itself (k = 0): the plane cuts the object as the box face does, a capped cut face.
+template <int GRAD, bool BIG, bool PROBE, bool COUNT, bool CLIP>
+__global__ __launch_bounds__(256) void isosurface_kernel(const RenderParams P, const IsoArgs<CLIP> X) {
   // tile and lane mapping of project_kernel / render_kernel
   int tx, ty;
   if (!tile_of_block(P, tx, ty)) return;  // whole workgroup: uniform
@@ -75,6 +86,7 @@ __global__ __launch_bounds__(256) void isosurface_kernel(const RenderParams P, c
     f3 o, d;
     float tnear;
     hit = ray_setup(P, x, y, o, d, tnear, tfar);  // volumeRender_kernel.cu:388-425
+    if constexpr (CLIP) hit = clip_interval(X.clip, o, d, hit, tnear, tfar);
     if (hit) {
       pos = mk(fmaf(d.x, tnear, o.x), fmaf(d.y, tnear, o.y), fmaf(d.z, tnear, o.z));
       step = mk(d.x * tstep, d.y * tstep, d.z * tstep);
@@ -282,26 +294,37 @@ __global__ __launch_bounds__(256) void isosurface_kernel(const RenderParams P, c
 // ------------------------------------------------------------------------------------------------
 // launch helper (called from vr_capi.hip)
 
+template <int GRAD, bool BIG, bool PROBE, bool CLIP>
+static void launch_k(const RenderParams &P, const IsoArgs<CLIP> &X, dim3 grid, hipStream_t s) {
+  if (P.steps) hipLaunchKernelGGL((isosurface_kernel<GRAD, BIG, PROBE, true, CLIP>), grid, dim3(256), 0, s, P, X);
+  else hipLaunchKernelGGL((isosurface_kernel<GRAD, BIG, PROBE, false, CLIP>), grid, dim3(256), 0, s, P, X);
+}
+
 template <int GRAD, bool BIG, bool PROBE>
-static void launch_c(const RenderParams &P, const IsoExtras &X, dim3 grid, hipStream_t s) {
-  if (P.steps) hipLaunchKernelGGL((isosurface_kernel<GRAD, BIG, PROBE, true>), grid, dim3(256), 0, s, P, X);
-  else hipLaunchKernelGGL((isosurface_kernel<GRAD, BIG, PROBE, false>), grid, dim3(256), 0, s, P, X);
+static void launch_c(const RenderParams &P, const IsoExtrasClip &X, dim3 grid, hipStream_t s) {
+  if (X.clip.n > 0) launch_k<GRAD, BIG, PROBE, true>(P, X, grid, s);
+  else launch_k<GRAD, BIG, PROBE, false>(P, static_cast<const IsoExtras &>(X), grid, s);
 }
 
 template <int GRAD>
-static void launch_g(const RenderParams &P, const IsoExtras &X, bool big, bool probe, dim3 grid, hipStream_t s) {
+static void launch_g(const RenderParams &P, const IsoExtrasClip &X, bool big, bool probe, dim3 grid, hipStream_t s) {
   if (big) probe ? launch_c<GRAD, true, true>(P, X, grid, s) : launch_c<GRAD, true, false>(P, X, grid, s);
   else probe ? launch_c<GRAD, false, true>(P, X, grid, s) : launch_c<GRAD, false, false>(P, X, grid, s);
 }
 
-// grad: 1 on-the-fly, 2 lookup; probe: leap empty space (needs P.occ and a level above 0)
+// grad: 1 on-the-fly, 2 lookup; probe: leap empty space (needs P.occ and a level above 0); clip: the
+// launch's plane set, or null / n == 0: the unclipped instantiations
 hipError_t launch_isosurface(const RenderParams &P, int grad, float level, float *depth, float *normal, bool big,
-                             bool probe, hipStream_t s) {
+                             bool probe, hipStream_t s, const ClipSet *clip) {
   if (P.part_cols <= 0 || P.height <= 0) return hipSuccess;
   if (grad != 1 && grad != 2) return hipErrorInvalidValue;
   const uint64_t ntx = (P.part_cols + 15) / 16, nty = (P.height + 15) / 16;
   const dim3 grid((unsigned)(ntx * nty));  // (tile_mode 0: row-major tiles)
-  const IsoExtras X{level, depth, normal};
+  IsoExtrasClip X{};
+  X.level = level;
+  X.depth = depth;
+  X.normal = normal;
+  if (clip) X.clip = *clip;
   probe = probe && P.occ != nullptr && P.occ_bx != 0u && level > 0.f;
   if (grad == 1) launch_g<1>(P, X, big, probe, grid, s);
   else launch_g<2>(P, X, big, probe, grid, s);

@@ -23,6 +23,7 @@
 #include <stdint.h>
 #include <math.h>
 
+#include "vr_clip.h"
 #include "vr_convert.h"
 #include "vr_device.h"
 #include "vr_sampling.h"
@@ -32,8 +33,9 @@ namespace vr {
 // MODE 0: no light sources (shade() contributes exactly 0); 1: on-the-fly gradient; 2: lookup.
 // SHARE: the gradient texture(s) have the emission texture's dims, so the unshifted axes of the
 // gradient taps (MODE 1) / all axes of the lookups (MODE 2) are the centre sample's.
-template <int MODE, bool AB_ALIAS, bool BIG, bool COUNT, bool SHARE, bool FAST>
-__global__ __launch_bounds__(256, VR_MIN_WAVES) void render_kernel(const RenderParams P) {
+// CLIP: the handle's clip planes shorten [tnear, tfar] after ray_setup (vr_clip.h); C is empty otherwise.
+template <int MODE, bool AB_ALIAS, bool BIG, bool COUNT, bool SHARE, bool FAST, bool CLIP>
+__global__ __launch_bounds__(256, VR_MIN_WAVES) void render_kernel(const RenderParams P, const ClipArg<CLIP> C) {
   // 16x16 pixel workgroup tile; wave w owns the 8x8 quadrant (w & 1, w >> 1); lane -> (x, y)
   // with y fastest so that the column-major output stores of a lane octet are contiguous.
   int tx, ty;
@@ -49,7 +51,8 @@ __global__ __launch_bounds__(256, VR_MIN_WAVES) void render_kernel(const RenderP
 
     f3 o, d;
     float tnear, tfar;
-    const bool hit = ray_setup(P, x, y, o, d, tnear, tfar);  // volumeRender_kernel.cu:388-425
+    bool hit = ray_setup(P, x, y, o, d, tnear, tfar);  // volumeRender_kernel.cu:388-425
+    if constexpr (CLIP) hit = clip_interval(C.set, o, d, hit, tnear, tfar);
     const f3 bmin = mk(P.bmin[0], P.bmin[1], P.bmin[2]);
 
     float sr = 0.f, sg = 0.f, sb = 0.f, sa = 0.f;
@@ -303,34 +306,44 @@ __global__ __launch_bounds__(256) void stats_kernel(const float *__restrict__ sr
 // ------------------------------------------------------------------------------------------------
 // launch helpers (called from vr_capi.hip)
 
-template <int MODE, bool AB, bool BIG, bool SH>
-static hipError_t launch4(const RenderParams &P, dim3 grid, hipStream_t s) {
+template <int MODE, bool AB, bool BIG, bool SH, bool CLIP>
+static hipError_t launch5(const RenderParams &P, const ClipArg<CLIP> &C, dim3 grid, hipStream_t s) {
   if (P.fast_shade) {
     if (P.steps)
-      hipLaunchKernelGGL((render_kernel<MODE, AB, BIG, true, SH, true>), grid, dim3(256), 0, s, P);
+      hipLaunchKernelGGL((render_kernel<MODE, AB, BIG, true, SH, true, CLIP>), grid, dim3(256), 0, s, P, C);
     else
-      hipLaunchKernelGGL((render_kernel<MODE, AB, BIG, false, SH, true>), grid, dim3(256), 0, s, P);
+      hipLaunchKernelGGL((render_kernel<MODE, AB, BIG, false, SH, true, CLIP>), grid, dim3(256), 0, s, P, C);
   } else {
     if (P.steps)
-      hipLaunchKernelGGL((render_kernel<MODE, AB, BIG, true, SH, false>), grid, dim3(256), 0, s, P);
+      hipLaunchKernelGGL((render_kernel<MODE, AB, BIG, true, SH, false, CLIP>), grid, dim3(256), 0, s, P, C);
     else
-      hipLaunchKernelGGL((render_kernel<MODE, AB, BIG, false, SH, false>), grid, dim3(256), 0, s, P);
+      hipLaunchKernelGGL((render_kernel<MODE, AB, BIG, false, SH, false, CLIP>), grid, dim3(256), 0, s, P, C);
   }
   return hipGetLastError();
 }
 
+template <int MODE, bool AB, bool BIG, bool SH>
+static hipError_t launch4(const RenderParams &P, const ClipSet *clip, dim3 grid, hipStream_t s) {
+  if (clip && clip->n > 0) return launch5<MODE, AB, BIG, SH, true>(P, ClipArg<true>{*clip}, grid, s);
+  return launch5<MODE, AB, BIG, SH, false>(P, ClipArg<false>{}, grid, s);
+}
+
 template <int MODE, bool AB>
-static hipError_t launch3(const RenderParams &P, bool big, bool share, dim3 grid, hipStream_t s) {
-  if (big) return share ? launch4<MODE, AB, true, true>(P, grid, s) : launch4<MODE, AB, true, false>(P, grid, s);
-  return share ? launch4<MODE, AB, false, true>(P, grid, s) : launch4<MODE, AB, false, false>(P, grid, s);
+static hipError_t launch3(const RenderParams &P, const ClipSet *clip, bool big, bool share, dim3 grid, hipStream_t s) {
+  if (big)
+    return share ? launch4<MODE, AB, true, true>(P, clip, grid, s) : launch4<MODE, AB, true, false>(P, clip, grid, s);
+  return share ? launch4<MODE, AB, false, true>(P, clip, grid, s) : launch4<MODE, AB, false, false>(P, clip, grid, s);
 }
 
 template <int MODE>
-static hipError_t launch2(const RenderParams &P, bool ab_alias, bool big, bool share, dim3 grid, hipStream_t s) {
-  return ab_alias ? launch3<MODE, true>(P, big, share, grid, s) : launch3<MODE, false>(P, big, share, grid, s);
+static hipError_t launch2(const RenderParams &P, const ClipSet *clip, bool ab_alias, bool big, bool share, dim3 grid,
+                          hipStream_t s) {
+  return ab_alias ? launch3<MODE, true>(P, clip, big, share, grid, s) : launch3<MODE, false>(P, clip, big, share, grid, s);
 }
 
-hipError_t launch_render(const RenderParams &P, int mode, bool ab_alias, bool big, bool share, hipStream_t s) {
+// clip: the launch's plane set (vr_clip.h), or null / n == 0: the unclipped instantiations
+hipError_t launch_render(const RenderParams &P, int mode, bool ab_alias, bool big, bool share, hipStream_t s,
+                         const ClipSet *clip) {
   if (P.part_cols <= 0 || P.height <= 0) return hipSuccess;
   const uint64_t ntx = (P.part_cols + 15) / 16, nty = (P.height + 15) / 16;
   uint64_t blocks = ntx * nty;
@@ -340,9 +353,9 @@ hipError_t launch_render(const RenderParams &P, int mode, bool ab_alias, bool bi
   }
   dim3 grid((unsigned)blocks);
   switch (mode) {
-    case 0: return launch2<0>(P, ab_alias, big, false, grid, s);
-    case 1: return launch2<1>(P, ab_alias, big, share, grid, s);
-    default: return launch2<2>(P, ab_alias, big, share, grid, s);
+    case 0: return launch2<0>(P, clip, ab_alias, big, false, grid, s);
+    case 1: return launch2<1>(P, clip, ab_alias, big, share, grid, s);
+    default: return launch2<2>(P, clip, ab_alias, big, share, grid, s);
   }
 }
 

@@ -26,7 +26,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
+#include <type_traits>
 
+#include "vr_clip.h"
 #include "vr_device.h"
 #include "vr_sampling.h"
 #include "vr_stage.h"
@@ -48,11 +50,19 @@ namespace vr {
 struct ProjectExtras {
   float *aux;
 };
+// The same for a clipped instantiation, with the plane set (vr_clip.h).  The unclipped kernels keep
+// the arguments they had before there were planes.
+struct ProjectExtrasClip : ProjectExtras {
+  ClipSet clip;
+};
+template <bool CLIP>
+using ProjectArgs = std::conditional_t<CLIP, ProjectExtrasClip, ProjectExtras>;
 
 // MODE 0: maximum-intensity projection (aux: t of the first maximum), 1: ray sum (aux: samples).
 // COUNT: steps[0] += samples visited (leaped ones included), steps[1] += samples fetched.
-template <int MODE, bool BIG, bool PROBE, bool COUNT>
-__global__ __launch_bounds__(256) void project_kernel(const RenderParams P, const ProjectExtras X) {
+// CLIP: the clip planes shorten [tnear, tfar] after ray_setup; the march and the leap start from there.
+template <int MODE, bool BIG, bool PROBE, bool COUNT, bool CLIP>
+__global__ __launch_bounds__(256) void project_kernel(const RenderParams P, const ProjectArgs<CLIP> X) {
   // 16x16 pixel workgroup tile; wave w owns the 8x8 quadrant (w & 1, w >> 1); lane -> (x, y) with y
   // fastest so that the column-major output stores of a lane octet are contiguous (render_kernel).
   int tx, ty;
@@ -74,6 +84,7 @@ __global__ __launch_bounds__(256) void project_kernel(const RenderParams P, cons
     f3 o, d;
     float tnear;
     hit = ray_setup(P, x, y, o, d, tnear, tfar);  // volumeRender_kernel.cu:388-425
+    if constexpr (CLIP) hit = clip_interval(X.clip, o, d, hit, tnear, tfar);
     if (hit) {
       pos = mk(fmaf(d.x, tnear, o.x), fmaf(d.y, tnear, o.y), fmaf(d.z, tnear, o.z));
       step = mk(d.x * tstep, d.y * tstep, d.z * tstep);
@@ -215,25 +226,35 @@ __global__ __launch_bounds__(256) void project_kernel(const RenderParams P, cons
 // ------------------------------------------------------------------------------------------------
 // launch helper (called from vr_capi.hip)
 
+template <int MODE, bool BIG, bool PROBE, bool CLIP>
+static void launch_k(const RenderParams &P, const ProjectArgs<CLIP> &X, dim3 grid, hipStream_t s) {
+  if (P.steps) hipLaunchKernelGGL((project_kernel<MODE, BIG, PROBE, true, CLIP>), grid, dim3(256), 0, s, P, X);
+  else hipLaunchKernelGGL((project_kernel<MODE, BIG, PROBE, false, CLIP>), grid, dim3(256), 0, s, P, X);
+}
+
 template <int MODE, bool BIG, bool PROBE>
-static void launch_c(const RenderParams &P, const ProjectExtras &X, dim3 grid, hipStream_t s) {
-  if (P.steps) hipLaunchKernelGGL((project_kernel<MODE, BIG, PROBE, true>), grid, dim3(256), 0, s, P, X);
-  else hipLaunchKernelGGL((project_kernel<MODE, BIG, PROBE, false>), grid, dim3(256), 0, s, P, X);
+static void launch_c(const RenderParams &P, const ProjectExtrasClip &X, dim3 grid, hipStream_t s) {
+  if (X.clip.n > 0) launch_k<MODE, BIG, PROBE, true>(P, X, grid, s);
+  else launch_k<MODE, BIG, PROBE, false>(P, static_cast<const ProjectExtras &>(X), grid, s);
 }
 
 template <int MODE>
-static void launch_m(const RenderParams &P, const ProjectExtras &X, bool big, bool probe, dim3 grid, hipStream_t s) {
+static void launch_m(const RenderParams &P, const ProjectExtrasClip &X, bool big, bool probe, dim3 grid, hipStream_t s) {
   if (big) probe ? launch_c<MODE, true, true>(P, X, grid, s) : launch_c<MODE, true, false>(P, X, grid, s);
   else probe ? launch_c<MODE, false, true>(P, X, grid, s) : launch_c<MODE, false, false>(P, X, grid, s);
 }
 
-// mode: vr_projection (0 maximum, 1 sum); probe: leap empty space (needs P.occ)
-hipError_t launch_project(const RenderParams &P, int mode, float *aux, bool big, bool probe, hipStream_t s) {
+// mode: vr_projection (0 maximum, 1 sum); probe: leap empty space (needs P.occ); clip: the launch's
+// plane set, or null / n == 0: the unclipped instantiations
+hipError_t launch_project(const RenderParams &P, int mode, float *aux, bool big, bool probe, hipStream_t s,
+                          const ClipSet *clip) {
   if (P.part_cols <= 0 || P.height <= 0) return hipSuccess;
   if (mode != 0 && mode != 1) return hipErrorInvalidValue;
   const uint64_t ntx = (P.part_cols + 15) / 16, nty = (P.height + 15) / 16;
   const dim3 grid((unsigned)(ntx * nty));  // (tile_mode 0: row-major tiles)
-  const ProjectExtras X{aux};
+  ProjectExtrasClip X{};
+  X.aux = aux;
+  if (clip) X.clip = *clip;
   probe = probe && P.occ != nullptr && P.occ_bx != 0u;
   if (mode == 0) launch_m<0>(P, X, big, probe, grid, s);
   else launch_m<1>(P, X, big, probe, grid, s);

@@ -27,7 +27,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
+#include <type_traits>
 
+#include "vr_clip.h"
 #include "vr_device.h"
 #include "vr_sampling.h"
 #include "vr_stage.h"
@@ -59,13 +61,21 @@ struct TransferExtras {
   int32_t ab_alias;      // the absorption texture is the emission texture (its sample is reused)
   float *alpha;          // the alpha plane, [plane_cols][H] as one plane of the image, or null
 };
+// The same for a clipped instantiation, with the plane set (vr_clip.h).  The unclipped kernels keep
+// the arguments they had before there were planes.
+struct TransferExtrasClip : TransferExtras {
+  ClipSet clip;
+};
+template <bool CLIP>
+using TransferArgs = std::conditional_t<CLIP, TransferExtrasClip, TransferExtras>;
 
 extern __shared__ float4 tf_lds[];
 
 // GRAD 0: no illumination term; 1: on-the-fly gradient (six taps of the gem binding); 2: lookup.
 // COUNT: steps[0] += samples visited (leaped ones included), steps[1] += samples fetched.
-template <int GRAD, bool BIG, bool PROBE, bool COUNT>
-__global__ __launch_bounds__(256) void transfer_kernel(const RenderParams P, const TransferExtras X) {
+// CLIP: the clip planes shorten [tnear, tfar] after ray_setup; the march and the leap start from there.
+template <int GRAD, bool BIG, bool PROBE, bool COUNT, bool CLIP>
+__global__ __launch_bounds__(256) void transfer_kernel(const RenderParams P, const TransferArgs<CLIP> X) {
   // tile and lane mapping of project_kernel / render_kernel
   int tx, ty;
   if (!tile_of_block(P, tx, ty)) return;  // whole workgroup: uniform
@@ -97,6 +107,7 @@ __global__ __launch_bounds__(256) void transfer_kernel(const RenderParams P, con
     f3 o, d;
     float tnear;
     hit = ray_setup(P, x, y, o, d, tnear, tfar);  // volumeRender_kernel.cu:388-425
+    if constexpr (CLIP) hit = clip_interval(X.clip, o, d, hit, tnear, tfar);
     if (hit) {
       pos = mk(fmaf(d.x, tnear, o.x), fmaf(d.y, tnear, o.y), fmaf(d.z, tnear, o.z));
       step = mk(d.x * tstep, d.y * tstep, d.z * tstep);
@@ -277,14 +288,20 @@ __global__ __launch_bounds__(256) void transfer_kernel(const RenderParams P, con
 // ------------------------------------------------------------------------------------------------
 // launch helper (called from vr_capi.hip)
 
+template <int GRAD, bool BIG, bool PROBE, bool CLIP>
+static void launch_k(const RenderParams &P, const TransferArgs<CLIP> &X, dim3 grid, size_t lds, hipStream_t s) {
+  if (P.steps) hipLaunchKernelGGL((transfer_kernel<GRAD, BIG, PROBE, true, CLIP>), grid, dim3(256), lds, s, P, X);
+  else hipLaunchKernelGGL((transfer_kernel<GRAD, BIG, PROBE, false, CLIP>), grid, dim3(256), lds, s, P, X);
+}
+
 template <int GRAD, bool BIG, bool PROBE>
-static void launch_c(const RenderParams &P, const TransferExtras &X, dim3 grid, size_t lds, hipStream_t s) {
-  if (P.steps) hipLaunchKernelGGL((transfer_kernel<GRAD, BIG, PROBE, true>), grid, dim3(256), lds, s, P, X);
-  else hipLaunchKernelGGL((transfer_kernel<GRAD, BIG, PROBE, false>), grid, dim3(256), lds, s, P, X);
+static void launch_c(const RenderParams &P, const TransferExtrasClip &X, dim3 grid, size_t lds, hipStream_t s) {
+  if (X.clip.n > 0) launch_k<GRAD, BIG, PROBE, true>(P, X, grid, lds, s);
+  else launch_k<GRAD, BIG, PROBE, false>(P, static_cast<const TransferExtras &>(X), grid, lds, s);
 }
 
 template <int GRAD>
-static void launch_g(const RenderParams &P, const TransferExtras &X, bool big, bool probe, dim3 grid, size_t lds,
+static void launch_g(const RenderParams &P, const TransferExtrasClip &X, bool big, bool probe, dim3 grid, size_t lds,
                      hipStream_t s) {
   if (big) probe ? launch_c<GRAD, true, true>(P, X, grid, lds, s) : launch_c<GRAD, true, false>(P, X, grid, lds, s);
   else probe ? launch_c<GRAD, false, true>(P, X, grid, lds, s) : launch_c<GRAD, false, false>(P, X, grid, lds, s);
@@ -296,16 +313,18 @@ uint32_t transfer_table_units(int32_t nc, int32_t na) {
 }
 
 // grad: 0 unlit, 1 on-the-fly, 2 lookup; probe: leap empty space (needs P.occ; the host has checked
-// that a leaped sample adds exactly 0)
+// that a leaped sample adds exactly 0); clip: the launch's plane set, or null / n == 0: the unclipped
+// instantiations
 hipError_t launch_transfer(const RenderParams &P, int grad, const float *tab, int32_t nc, int32_t na, float clo,
                            float cinv, float alo, float ainv, int32_t coord, bool ab_alias, float *alpha, bool big,
-                           bool probe, hipStream_t s) {
+                           bool probe, hipStream_t s, const ClipSet *clip) {
   if (P.part_cols <= 0 || P.height <= 0) return hipSuccess;
   if (grad < 0 || grad > 2 || nc < 2 || nc > 1024 || na == 1 || na < 0 || na > 1024 || !tab)
     return hipErrorInvalidValue;
   const uint64_t ntx = (P.part_cols + 15) / 16, nty = (P.height + 15) / 16;
   const dim3 grid((unsigned)(ntx * nty));  // (tile_mode 0: row-major tiles)
-  TransferExtras X;
+  TransferExtrasClip X{};
+  if (clip) X.clip = *clip;
   X.tab = reinterpret_cast<const float4 *>(tab);
   X.n16 = transfer_table_units(nc, na);
   X.nc = nc;

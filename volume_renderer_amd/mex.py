@@ -397,6 +397,53 @@ def transfer_lookup_host(table, lim, c) -> np.ndarray:
     return out[0] if vec else out
 
 
+def clip_planes(planes):
+    """The vr_clip_plane array of a plane set: `planes` n x 4, rows [n0 n1 n2 offset] keeping
+    n . q + offset >= 0 of the normalized volume coordinate q in the dimension order of Data (None,
+    False or an empty array: no planes).  Returns (array or None, n); the library checks the values."""
+    if planes is None or _is_false(planes):
+        return None, 0
+    a = np.asarray(planes, dtype=np.float32)
+    if a.size == 0:
+        return None, 0
+    if a.ndim == 1 and a.size == 4:
+        a = a.reshape(1, 4)
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise _lib.VrError(1, "clip planes must be an n x 4 matrix with rows [n0 n1 n2 offset]")
+    arr = (_lib.VrClipPlane * a.shape[0])()
+    for i in range(a.shape[0]):
+        for k in range(3):
+            arr[i].normal[k] = a[i, k]
+        arr[i].offset = a[i, 3]
+    return arr, int(a.shape[0])
+
+
+def set_clip(handle, planes) -> None:
+    """vr_set_clip: replace the handle's clip planes (clip_planes(); None / False / [] clears them)."""
+    arr, n = clip_planes(planes)
+    check(lib().vr_set_clip(_handle(handle), arr, n))
+
+
+def get_clip(handle) -> np.ndarray:
+    """vr_get_clip: the handle's clip planes as set, n x 4 single (0 x 4: none)."""
+    arr = (_lib.VrClipPlane * _lib.VR_CLIP_MAX)()
+    n = ctypes.c_int32(0)
+    check(lib().vr_get_clip(_handle(handle), arr, ctypes.byref(n)))
+    return np.array([[arr[i].normal[0], arr[i].normal[1], arr[i].normal[2], arr[i].offset] for i in range(n.value)],
+                    np.float32).reshape(n.value, 4)
+
+
+def clip_convert_host(planes, bmin, bscale) -> np.ndarray:
+    """vr_clip_convert_host: the per-launch conversion of a plane set for the box (bmin, bscale), rows
+    [N0 N1 N2 D] keeping N . p + D >= 0 of the world position p."""
+    arr, n = clip_planes(planes)
+    out = np.zeros((n, 4), np.float32)
+    b0 = (ctypes.c_float * 3)(*[float(x) for x in _f32(bmin, 3, "bmin")])
+    b1 = (ctypes.c_float * 3)(*[float(x) for x in _f32(bscale, 3, "bscale")])
+    check(lib().vr_clip_convert_host(arr, n, b0, b1, out.ctypes.data_as(ctypes.c_void_p)))
+    return out
+
+
 def set_option(name: str, value: int) -> None:
     """vr_set_option: a process-wide library option (include/vrhip.h)."""
     check(lib().vr_set_option(name.encode(), int(value)))
@@ -534,7 +581,7 @@ def _group_devices():
 def volumeRender(cmd, *args):
     """The `volumeRender` mex: commands 'new', 'delete', 'mem_info', 'sync_volumes', 'render' (and
     'render_stereo', 'render_channels', 'render_projection', 'render_isosurface', 'render_transfer',
-    which the reference does not have)."""
+    'set_clip', which the reference does not have)."""
     nrhs = 1 + len(args)
     if not isinstance(cmd, str) or len(cmd) >= 64:
         raise _lib.VrError(1, "First input should be a command string less than 64 characters long.")
@@ -581,6 +628,18 @@ def volumeRender(cmd, *args):
                                     ctypes.byref(flag), ctypes.byref(flag) if nrhs != 7 else None, None))
         if nrhs > 9:
             warnings.warn("SyncVolumes: Unexpected arguments ignored.")
+        return None
+    if cmd == "set_clip":  # ('set_clip', h, planes): planes 4 x n single, columns [n0; n1; n2; offset]; [] / false clears
+        if nrhs < 3:
+            raise _lib.VrError(1, "insufficient parameter!")
+        pl = args[1]
+        if not (pl is None or _is_false(pl)):
+            pl = np.asarray(pl)
+            if pl.size and (pl.ndim != 2 or pl.shape[0] != 4):
+                raise _lib.VrError(1, "set_clip: planes must be a 4 x n matrix with columns [n0; n1; n2; offset]")
+            pl = pl.T
+        arr, n = clip_planes(pl)
+        check(L.vr_set_clip(h, arr, n))
         return None
     if cmd == "render_stereo":  # fused stereo pair (vr_render_stereo): args as 'render' + base
         ra, keep = render_args(*args[1:10])

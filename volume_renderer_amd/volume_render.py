@@ -81,6 +81,11 @@ class VolumeRender:
         self.RotationMatrix = np.eye(3)
         self.ImageResolution = np.array([0, 0])
         self.TimeLastMemSync = np.uint64(0)
+        # clip planes (vr_set_clip): n x 4, rows [n0 n1 n2 offset] keeping n . q + offset >= 0 of the
+        # normalized volume coordinate q in the dimension order of Data; empty: none.  Sent to the
+        # handle before a render whenever they differ from what it holds (_apply_clip).
+        self.ClipPlanes = np.zeros((0, 4), dtype=np.float32)
+        object.__setattr__(self, "_clip_applied", np.zeros((0, 4), dtype=np.float32))
         if VolumeRender._default_reflection is None:
             VolumeRender._default_reflection = Volume(1)
         # observable properties: defaults are assigned without firing the listener
@@ -114,6 +119,14 @@ class VolumeRender:
             val = np.asarray(val, dtype=np.float64).reshape(2)
         elif name == "RotationMatrix":
             val = np.asarray(val, dtype=np.float64).reshape(3, 3)
+        elif name == "ClipPlanes":
+            val = np.zeros((0, 4), np.float32) if val is None or _is_logical(val) else np.asarray(val, dtype=np.float32)
+            if val.size == 0:
+                val = np.zeros((0, 4), np.float32)
+            elif val.ndim == 1 and val.size == 4:
+                val = val.reshape(1, 4)
+            if val.ndim != 2 or val.shape[1] != 4:
+                raise TypeError("ClipPlanes must be an n x 4 matrix with rows [n0 n1 n2 offset]")
         object.__setattr__(self, name, val)
         if name in _VOLUME_PROPS and isinstance(val, Volume):
             val.TimeLastUpdate = timestamp()
@@ -140,6 +153,12 @@ class VolumeRender:
             volumeRender("sync_volumes", self.objectHandle, self.TimeLastMemSync, self.VolumeEmission,
                          self.VolumeReflection, self.VolumeAbsorption)
         self.TimeLastMemSync = timestamp()
+
+    def _apply_clip(self) -> None:
+        """'set_clip' (4 x n, columns [n0; n1; n2; offset]) if ClipPlanes changed since the last one."""
+        if not np.array_equal(self.ClipPlanes, self._clip_applied):
+            volumeRender("set_clip", self.objectHandle, np.asfortranarray(self.ClipPlanes.T))
+            object.__setattr__(self, "_clip_applied", self.ClipPlanes.copy())
 
     def memInfo(self) -> None:
         volumeRender("mem_info", self.objectHandle)
@@ -199,6 +218,7 @@ class VolumeRender:
     def _p_project(self, camera_x_offset, resolution, mode):
         """Validate and sync the volumes as _p_render does, then 'render_projection'."""
         self._validate_volumes()
+        self._apply_clip()
         self.syncVolumes()
         return volumeRender("render_projection", self.objectHandle, *self._render_argv(camera_x_offset, resolution),
                             mode)
@@ -226,6 +246,7 @@ class VolumeRender:
         """Validate and sync the volumes as _p_render does (the lights and the LUT travel in the
         render arguments), then 'render_isosurface'."""
         self._validate_volumes()
+        self._apply_clip()
         self.syncVolumes()
         return volumeRender("render_isosurface", self.objectHandle, *self._render_argv(camera_x_offset, resolution),
                             level)
@@ -256,6 +277,7 @@ class VolumeRender:
         """Validate and sync the volumes as _p_render does (the lights and the LUT travel in the
         render arguments), then 'render_transfer'."""
         self._validate_volumes()
+        self._apply_clip()
         self.syncVolumes()
         cm = np.asfortranarray(colormap, dtype=np.float32)
         am = False if alphamap is None else np.asarray(alphamap, dtype=np.float32).reshape(-1, 1)
@@ -304,6 +326,7 @@ class VolumeRender:
         chans = []
         for r in renders:
             with_grads = r._validate_volumes()
+            r._apply_clip()  # (a channel with planes: the library answers VR_ERR_UNSUPPORTED)
             argv = r._render_argv(np.float32(-base if stereo else 0.0), resolution)
             vols = [r.VolumeEmission, r.VolumeReflection, r.VolumeAbsorption]
             if with_grads:
@@ -355,6 +378,7 @@ class VolumeRender:
             if not all(isinstance(g, Volume) for g in grads):
                 raise ValueError("All gradient dimensions need to be set and of type Volume!")
             with_grads = True
+        self._apply_clip()
         self.syncVolumes()
         factors = np.array([self.FactorEmission, self.FactorReflection, self.FactorAbsorption])
         props = np.array([camera_x_offset, self.FocalLength, self.DistanceToObject], dtype=np.float64)
