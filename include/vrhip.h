@@ -548,6 +548,27 @@ int64_t vr_hip_errors(char *buf, size_t buflen);
  * bench.py names the kernel it times with it and keys the profiler's counters to it. */
 int vr_last_march_kernel(char *buf, size_t buflen);
 
+/* The launch-wide decisions of the last frame this process built (vr_capi.hip build_frame: every
+ * render call builds one per view before it launches), one bit each.  The host takes them from the
+ * upload statistics of the bound buffers, the factors, the colours and the bindings, and the kernels
+ * trust them (DESIGN.md "Launch-wide decisions"); the tests read them back to assert which side of a
+ * decision a scene took.  Read-only: nothing is selected through this call. */
+enum vr_launch_flag {
+  VR_LF_TAME = 1 << 0,       /* every flag below up to LUT_OK holds and tstep is finite and positive: the march
+                                runs without per-sample range and coordinate tests, and probes, leaps and pre-leaps */
+  VR_LF_SMALL_X = 1 << 1,    /* every |Fa * ab(p) * tstep| < 2^-7: the exponential's Taylor form, no range test */
+  VR_LF_EDS_FINITE = 1 << 2, /* every |Fe * em(p) * tstep| is finite */
+  VR_LF_SKIP_EMPTY = 1 << 3, /* skip_empty is non-zero: a sample with alpha == 0 is an exact no-op and is skipped */
+  VR_LF_RE_OK = 1 << 4,      /* the reflection texture is the emission texture or a single voxel */
+  VR_LF_LUT_OK = 1 << 5,     /* no lights, or a small, z-paired, non-1x1x1 LUT of at most 8192 texels per axis */
+  VR_LF_TAP_HALF = 1 << 6,   /* the on-the-fly gradient's taps lie exactly half a texel from the centre */
+  VR_LF_AB_ALIAS = 1 << 7,   /* the absorption texture is the emission texture */
+  VR_LF_SHARE = 1 << 8,      /* the gradient reads share the centre sample's axes */
+  VR_LF_BIG = 1 << 9,        /* 64-bit texture offsets */
+  VR_LF_OCC = 1 << 10        /* an occupancy map is bound (the emission buffer has one) */
+};
+int vr_last_launch_flags(uint32_t *flags);
+
 /* Process-wide options (round 6; no reference counterpart).  "test_switches" = 1 lets the library
  * read the kernel-variant and schedule switches the GPU tests and the measurement tools set through
  * the environment (VR_NO_LDS, VR_DEPTH_LANES, VR_SCHED, ... -- INTEGRATION.md "Runtime switches");

@@ -25,6 +25,9 @@ VR_PROJ_MIP, VR_PROJ_SUM = 0, 1
 VR_TF_VALUE, VR_TF_DEPTH = 0, 1
 VR_TF_MAX_ENTRIES = 1024
 VR_CLIP_MAX = 6
+# enum vr_launch_flag: the bits of vr_last_launch_flags, in bit order
+LAUNCH_FLAGS = ("tame", "small_x", "eds_finite", "skip_empty", "re_ok", "lut_ok", "tap_half", "ab_alias", "share",
+                "big", "occ")
 
 
 class VrVolume(ctypes.Structure):
@@ -136,6 +139,7 @@ SIGNATURES = [
     ("vr_last_error", c_char_p, []),
     ("vr_hip_errors", c_int64, [c_char_p, c_size_t]),
     ("vr_last_march_kernel", c_int, [c_char_p, c_size_t]),
+    ("vr_last_launch_flags", c_int, [POINTER(c_uint32)]),
     ("vr_set_option", c_int, [c_char_p, c_int64]),
     ("vr_version", c_char_p, []),
 ]

@@ -169,6 +169,10 @@ void note_march_kernel(bool fast, int K, int mode, bool ab, bool count, bool sha
 }  // namespace vr
 
 namespace {
+uint32_t g_last_launch_flags = 0;  // vr_last_launch_flags: set by build_frame, under g_mu like the frame itself
+}
+
+namespace {
 
 thread_local std::string g_last_error;
 
@@ -733,6 +737,7 @@ struct Frame {
   double drift1[3] = {0, 0, 0};  // staging-halo rounding margin per chunk sample (set_chunk_halo)
   int mode = 0;
   bool ab_alias = false, big = false, share = false;
+  uint32_t flags = 0;  // enum vr_launch_flag: what vr_last_launch_flags reports of this frame
   bool degenerate = false;
   vr_context::Schedule *sched_copy = nullptr;  // a timed full-frame launch: copy its durations back
   vr_context::Schedule *sched = nullptr;       // the launch shape's schedule (attach_schedule)
@@ -946,6 +951,7 @@ int build_frame(vr_context *h, const vr_render_args *a, Frame &F, uint64_t depth
     P.tame = (P.skip_empty && P.eds_finite && P.small_x && re_ok && lut_ok && step_ok && !diag_flag("VR_NO_TAME")) ? 1
                                                                                                             : 0;
     P.re_mask = P.re_is_em ? 0xffffffffu : 0u;
+    F.flags = (re_ok ? VR_LF_RE_OK : 0u) | (lut_ok ? VR_LF_LUT_OK : 0u);
   }
   F.big = is_big(P.em) || is_big(P.ab) || is_big(P.re) || is_big(P.gem) || is_big(P.gx) || is_big(P.gy) ||
           is_big(P.gz) || test_flag("VR_FORCE_BIG");  // test switch: the 64-bit path on small volumes
@@ -969,6 +975,11 @@ int build_frame(vr_context *h, const vr_render_args *a, Frame &F, uint64_t depth
     if (v > 0 && v < (long)P.max_steps) P.max_steps = (int32_t)v;
   }
   F.degenerate = !finite;  // no synced emission volume: nothing to march through (renders zeros)
+  F.flags |= (P.tame ? VR_LF_TAME : 0u) | (P.small_x ? VR_LF_SMALL_X : 0u) | (P.eds_finite ? VR_LF_EDS_FINITE : 0u) |
+             (P.skip_empty ? VR_LF_SKIP_EMPTY : 0u) | (P.tap_half ? VR_LF_TAP_HALF : 0u) |
+             (F.ab_alias ? VR_LF_AB_ALIAS : 0u) | (F.share ? VR_LF_SHARE : 0u) | (F.big ? VR_LF_BIG : 0u) |
+             (P.occ ? VR_LF_OCC : 0u);
+  g_last_launch_flags = F.flags;
   return VR_OK;
 }
 
@@ -1968,6 +1979,7 @@ int do_render_slab(vr_context *h, const vr_render_args *a, const vr_slab *sl, co
     P.tap_half = half_texel_taps(P, F.mode, (float)D);  // judged on the whole volume, as one render
     for (int i = 0; i < 3; ++i)  // (the cube's n / 2 per axis, the whole volume's depth on z)
       P.cube_hs[i] = P.tap_half ? (i == 0 ? P.em.fnx : i == 1 ? P.em.fny : (float)D) * 0.5f : 0.f;
+    g_last_launch_flags = F.flags = (F.flags & ~(uint32_t)VR_LF_TAP_HALF) | (P.tap_half ? VR_LF_TAP_HALF : 0u);
   }
   P.slab_dir = sl->direction;
   P.slab_in = d_in;
@@ -3473,6 +3485,13 @@ int vr_last_march_kernel(char *buf, size_t buflen) {
     std::memcpy(buf, s.data(), n);
     buf[n] = 0;
   }
+  return VR_OK;
+}
+
+int vr_last_launch_flags(uint32_t *flags) {
+  if (!flags) return fail(VR_ERR_ARGUMENT, "vr_last_launch_flags: flags is NULL");
+  std::lock_guard<std::mutex> lk(g_mu);
+  *flags = g_last_launch_flags;
   return VR_OK;
 }
 

@@ -466,6 +466,15 @@ def last_march_kernel() -> str:
     return buf.value.decode()
 
 
+def last_launch_flags() -> dict:
+    """The launch-wide decisions of the last frame this process built (vr_last_launch_flags), by
+    name: tame, small_x, eds_finite, skip_empty, re_ok, lut_ok, tap_half, ab_alias, share, big and
+    occ (an occupancy map is bound), each a bool."""
+    word = ctypes.c_uint32(0)
+    check(lib().vr_last_launch_flags(ctypes.byref(word)))
+    return {name: bool(word.value >> bit & 1) for bit, name in enumerate(_lib.LAUNCH_FLAGS)}
+
+
 def assemble_partitions(d_parts: int, width: int, height: int, block_cols: int, num_parts: int, max_cols: int,
                         d_out: int, stream: int = 0) -> None:
     check(lib().vr_assemble_partitions(ctypes.c_void_p(int(d_parts)), int(width), int(height), int(block_cols),
