@@ -10,8 +10,17 @@
 
 #include "vr_device.h"
 #include "vr_sampling.h"
+#include "vr_udiv.h"
 
 namespace vr {
+
+#ifndef VR_UDIV_MAGIC
+// 1 (round 15): the staging copy's per-lane quotients by the wave-uniform box extents (stage_box) as
+// udiv_small, the magics from a table in constant memory (one scalar load each); 0 (A/B, tests):
+// the compiler's u32 division sequences
+#define VR_UDIV_MAGIC 1
+#endif
+static __constant__ const UdivTab udiv_tab = make_udiv_tab();
 
 // Wave slot sizes (floats).  The march kernel is built for both and the host picks per frame
 // from the camera's texels per pixel (vr_capi.hip): the 8x8-ray footprint grows with it.
@@ -92,6 +101,39 @@ __device__ __forceinline__ int wave_min2(int v) {
   const auto p32 = __builtin_amdgcn_permlane32_swap(v, v, false, false);
   v = pk_min((int)p32[0], (int)p32[1]);
   return __builtin_amdgcn_readfirstlane(v);
+}
+#ifndef VR_JOINT_MIN
+#define VR_JOINT_MIN 1  // 0 (A/B, tests): three wave_min2 one after another
+#endif
+// wave_min2 of three words at once (round 15): the swaps exchange halves of two registers, so the
+// 64 -> 32 and 32 -> 16 steps of several words share their instructions, and the four row rotations
+// run once, on a register whose four rows belong to different words.
+//   permlane32_swap(a, b): [a.lo32 | b.lo32] and [a.hi32 | b.hi32]; their min holds a's 32-lane
+//     reduction in lanes 0..31 and b's in lanes 32..63 (x1); c against itself likewise (x2)
+//   permlane16_swap(x1, x2) exchanges the odd rows of x1 with the even rows of x2: rows
+//     [a0 c0 b0 c2] and [a1 c1 b1 c3]; their min has a, c, b, c reduced to one row each
+//   row_ror 8, 4, 2, 1 finish every row; lanes 0, 32 and 16 hold a, b and c.
+// 18 VALU and one chain of dependent steps, where three wave_min2 are 45 and three chains.
+__device__ __forceinline__ void wave_min2x3(int a, int b, int c, int &ra, int &rb, int &rc) {
+#if VR_JOINT_MIN
+  const auto s1 = __builtin_amdgcn_permlane32_swap(a, b, false, false);
+  const int x1 = pk_min((int)s1[0], (int)s1[1]);
+  const auto s2 = __builtin_amdgcn_permlane32_swap(c, c, false, false);
+  const int x2 = pk_min((int)s2[0], (int)s2[1]);
+  const auto s3 = __builtin_amdgcn_permlane16_swap(x1, x2, false, false);
+  int v = pk_min((int)s3[0], (int)s3[1]);
+  v = pk_min(v, row_ror<0x128>(v));
+  v = pk_min(v, row_ror<0x124>(v));
+  v = pk_min(v, row_ror<0x122>(v));
+  v = pk_min(v, row_ror<0x121>(v));
+  ra = __builtin_amdgcn_readlane(v, 0);
+  rb = __builtin_amdgcn_readlane(v, 32);
+  rc = __builtin_amdgcn_readlane(v, 16);
+#else
+  ra = wave_min2(a);
+  rb = wave_min2(b);
+  rc = wave_min2(c);
+#endif
 }
 __device__ __forceinline__ int pk2(int lo16, int hi16) { return (lo16 & 0xffff) | (int)((uint32_t)hi16 << 16); }
 __device__ __forceinline__ int pk_lo(int v) { return (int)(short)(v & 0xffff); }
@@ -370,16 +412,34 @@ __device__ __forceinline__ bool stage_box(float *L, const DevTex &t, const Box &
   if (VR_STAGE_GLDS && B.px == ex && B.pxy == ex * ey &&
       (BIG || (uint64_t)t.pxy * (uint64_t)B.ez * 4u < 0xFFFFFFFFull))
     return stage_box_glds<BIG>(L, t, B, lane);
-  if (ex > 64) return stage_box_elems(L, t, B, lane);
-  if (!BIG && (uint64_t)t.pxy * (uint64_t)B.ez * 4u >= 0xFFFFFFFFull)  // 32-bit byte offsets overflow
+  const int rows = ey * B.ez;
+  // (32-bit byte offsets overflow; rows: the bound of udiv_small's dividend below, which no slot's box
+  // reaches)
+  if (ex > 64 || (!BIG && (uint64_t)t.pxy * (uint64_t)B.ez * 4u >= 0xFFFFFFFFull) ||
+      (VR_UDIV_MAGIC && rows > (int)UDIV_MAX_N - 64))
     return stage_box_elems(L, t, B, lane);
   typedef typename std::conditional<BIG, uint64_t, uint32_t>::type off_t;
+#if VR_UDIV_MAGIC
+  // The lane's row slot, x, y, z and pass count: quotients by the wave-uniform ex, 64 / ex and ey as
+  // udiv_small, the magics from one scalar load each.  Dividends: 64, lane and rr are at most 64; the
+  // rounded-up row count is below rows + 64, and rows * ex <= the slot size (2560 floats at most), so
+  // it is below 4096 -- a box of more rows (no slot holds one) takes the element-wise copy above.  ey
+  // may exceed 64 (a narrow box): rr < 64 then has the quotient 0 by 64 as well.
+  const UdivEntry ue = udiv_tab.e[ex];
+  const uint32_t mey = udiv_tab.e[min(ey, 64)].m;
+  const int per = (int)((64u * ue.m) >> UDIV_SHIFT);  // rows per pass (wave-uniform, SALU)
+  const int rr = (int)udiv_small((uint32_t)lane, ue.m), xr = (int)urem_small((uint32_t)lane, (uint32_t)rr, (uint32_t)ex);
+  // passes with a row for this lane
+  const int n = rr < per ? (int)udiv_small((uint32_t)(rows - rr + per - 1), ue.mper) : 0;
+  const int z = (int)udiv_small((uint32_t)rr, mey);
+  int y = (int)urem_small((uint32_t)rr, (uint32_t)z, (uint32_t)ey);
+#else
   const int per = 64 / ex;  // rows per pass (wave-uniform)
   const int rr = lane / ex, xr = lane - rr * ex;
-  const int rows = ey * B.ez;
   const int n = rr < per ? (rows - rr + per - 1) / per : 0;  // passes with a row for this lane
   int y = rr % ey;
   const int z = rr / ey;
+#endif
   const char *base = reinterpret_cast<const char *>(
       t.p + ((uint64_t)B.rz * t.pxy + (uint64_t)B.ry * t.px + (uint64_t)B.rx));  // uniform
   off_t g = ((off_t)z * t.pxy + (off_t)y * t.px + (off_t)xr) * 4u;               // bytes
@@ -460,9 +520,9 @@ __device__ __forceinline__ void plan_chunk(const RenderParams &P, bool alive, co
       // padded bounds lie in [0, n + 1] (and the dead-lane sentinels are clamped to +-16383), so
       // they fit int16 fields: lo x/y, lo z / -hi x, -hi y / -hi z, each pair in one reduction
       const int c = 16383;
-      const int a = wave_min2(pk2(min(lo[0], c), min(lo[1], c)));
-      const int b = wave_min2(pk2(min(lo[2], c), min(-hi[0], c)));
-      const int d = wave_min2(pk2(min(-hi[1], c), min(-hi[2], c)));
+      int a, b, d;
+      wave_min2x3(pk2(min(lo[0], c), min(lo[1], c)), pk2(min(lo[2], c), min(-hi[0], c)),
+                  pk2(min(-hi[1], c), min(-hi[2], c)), a, b, d);
       B.rx = pk_lo(a);
       B.ry = pk_hi(a);
       B.rz = pk_lo(b);
@@ -561,9 +621,10 @@ __device__ __forceinline__ int probe_run(const RenderParams &P, KParams kp0, boo
   }
   // brick ranges of the box (padded coordinates >> VR_OCC_LOG): lo in the low, -hi in the high int16 field
   const int c = 16383;
-  const int a = wave_min2(pk2(min(lo[0] >> VR_OCC_LOG, c), min(lo[1] >> VR_OCC_LOG, c)));
-  const int b = wave_min2(pk2(min(lo[2] >> VR_OCC_LOG, c), min(-(hi[0] >> VR_OCC_LOG), c)));
-  const int d = wave_min2(pk2(min(-(hi[1] >> VR_OCC_LOG), c), min(-(hi[2] >> VR_OCC_LOG), c)));
+  int a, b, d;
+  wave_min2x3(pk2(min(lo[0] >> VR_OCC_LOG, c), min(lo[1] >> VR_OCC_LOG, c)),
+              pk2(min(lo[2] >> VR_OCC_LOG, c), min(-(hi[0] >> VR_OCC_LOG), c)),
+              pk2(min(-(hi[1] >> VR_OCC_LOG), c), min(-(hi[2] >> VR_OCC_LOG), c)), a, b, d);
   const int bx = pk_lo(a), by = pk_hi(a), bz = pk_lo(b);
   const int cx = -pk_hi(b) - bx + 1, cy = -pk_lo(d) - by + 1, cz = -pk_hi(d) - bz + 1;
   if (cx <= 0 || cy <= 0 || cz <= 0) return 1;  // no live ray
