@@ -432,6 +432,58 @@ int vr_get_clip(vr_context *h, vr_clip_plane *planes /* VR_CLIP_MAX */, int32_t 
 int vr_clip_convert_host(const vr_clip_plane *planes, int32_t n, const float bmin[3], const float bscale[3],
                          float *out /* [n][4] */);
 
+/* --- label volume with per-label gains: fade segmented regions without a re-upload (no reference
+ * counterpart; examples/example4.m rewrites VolumeEmission.Data(mask) on the host per frame) ---------
+ * A label volume (uint8, one label per voxel) stays resident beside the handle's emission volume, and a
+ * gain table (one fp32 gain per label) is state of the handle.  The resident emission buffer, its upload
+ * statistics and its occupancy map are re-derived on the device from the unmodified upload; the render
+ * calls read an ordinary resident volume and are unchanged.
+ * Value.  For voxel i with label l = labels[i] the resident voxel is l < n ? src[i] * gains[l] : src[i]:
+ * one fp32 multiplication rounded once -- MATLAB's single(gain) * Data(i), numpy's float32 product --
+ * of src[i], the resident fp32 voxel after the typed upload's widening or UNORM division.  Labels at or
+ * above n have gain 1 and are copied, not multiplied.  A NaN voxel stays NaN; +-0 and inf follow IEEE
+ * (x * 0.0f keeps the sign, inf * 0 is NaN).  With n = 0 or no labels the buffer holds the unmodified
+ * voxels bit for bit.  So the state equals vr_sync_volumes of the host-rewritten volume bit for bit: the
+ * padded data and its apron (the edge replicate of the modulated interior), nonfinite and maxabs of the
+ * modulated values (the launch-wide decisions of vr_last_launch_flags follow them), an occupancy map of
+ * the modulated data, and a new upload version (launch schedules keyed on the upload are not reused).
+ * Labels.  dtype must be VR_U8 without VR_DTYPE_UNORM (VR_ERR_ARGUMENT otherwise); location host or
+ * device; stored dense on the device, one byte per voxel.  A repeated vr_sync_labels of the same Volume
+ * identity (data pointer, TimeLastUpdate != 0, dims, location) is not uploaded again.  NULL, or an empty
+ * volume, drops the labels.  The dims must equal those of the handle's emission volume whenever both are
+ * present and n > 0: the call that notices -- vr_sync_labels (the previous labels stay),
+ * vr_set_label_gains (the previous table stays) or vr_sync_volumes (the new volume is resident,
+ * unmodified) -- returns VR_ERR_ARGUMENT with a message that names the labels.
+ * Gains.  n in 0..256 (n = 0 clears the table, gains may then be NULL), every gain finite, negative
+ * allowed; gains NULL with n > 0: each VR_ERR_ARGUMENT, checked before the handle (they need no device).
+ * vr_get_label_gains writes the n gains as set into gains[0 .. n-1] (room for 256) and n into *n.
+ * What is modulated.  The device buffer that the handle's last vr_sync_volumes bound as the emission
+ * texture.  Absorption or reflection that alias it (the reference's default: VolumeAbsorption is the
+ * same Volume) sample the same buffer and follow; a separately uploaded absorption or reflection
+ * volume, the gradient volumes of lookup mode and the LUT are not touched.
+ * When.  Eagerly: inside vr_sync_labels, inside vr_set_label_gains and at the end of vr_sync_volumes
+ * (also per channel in vr_render_channels), whenever emission, labels and n > 0 are all present, in
+ * whatever order they arrived; nothing is written when nothing changed.  A sync of a changed emission
+ * volume uploads it and re-applies the gains; a sync of an unchanged one keeps the modulation.  A rewrite
+ * waits for every launch that reads the buffer, so a *_device render in flight on any stream sees the
+ * gains that were set when it was launched.
+ * Memory.  The label bytes and, while gains are set, an unmodified copy of the emission volume count in
+ * the handle's required memory (VR_ERR_VRAM when they do not fit) and appear in 'mem_info'; vr_delete
+ * frees them.
+ * vr_sync_labels, and vr_set_label_gains with n > 0, on a multi-device group handle: VR_ERR_UNSUPPORTED,
+ * the message names the labels.  With no labels and no gains every call allocates, uploads and launches
+ * what it does without this feature. */
+int vr_sync_labels(vr_context *h, const vr_volume *labels);           /* NULL drops them */
+int vr_set_label_gains(vr_context *h, const float *gains, int32_t n); /* n = 0 clears   */
+int vr_get_label_gains(vr_context *h, float *gains /* 256 */, int32_t *n);
+
+/* The value rule above on the CPU (needs no device): dst[i] = labels[i] < n ? src[i] * gains[labels[i]] :
+ * src[i] for count voxels, by the inline function the kernel evaluates (csrc/vr_labels.h).  The argument
+ * checks of vr_set_label_gains; a NULL src or dst, or NULL labels with n > 0, with count > 0 is
+ * VR_ERR_ARGUMENT. */
+int vr_label_gain_host(const float *src, const uint8_t *labels, const float *gains, int32_t n, uint64_t count,
+                       float *dst);
+
 /* The kernel's table lookup on the CPU (needs no device): out[k * m + j] = L(table plane k, n, lim,
  * c[j]) for the ncomp planes table[k * n + i].  VR_ERR_ARGUMENT for a NULL pointer with m > 0, an n
  * outside 2..VR_TF_MAX_ENTRIES, ncomp < 1, or limits that are not finite with lo < hi. */

@@ -358,5 +358,67 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     check(vr_set_clip(h, static_cast<const vr_clip_plane *>(mxGetData(pl)), (int32_t)n));
     return;
   }
+  if (!strcmp(cmd, "sync_labels")) {
+    // volumeRender('sync_labels', h, labels) (vr_sync_labels): labels a uint8 array of the size of the
+    // emission volume's Data (one label per voxel), or a RawVolume of uint8 (its TimeLastUpdate spares a
+    // repeated upload); [] or false drops them.  The labels stay with the handle until the next 'sync_labels'.
+    if (nlhs > 0) mexErrMsgTxt("Too many output arguments.");
+    if (nrhs < 3) mexErrMsgTxt("insufficient parameter!");
+    if (nrhs > 3) mexErrMsgTxt("sync_labels: too many input arguments");
+    const mxArray *lb = prhs[2];
+    if (mxIsClass(lb, "logical")) {
+      if (mxGetNumberOfElements(lb) != 1 || mxGetScalar(lb) != 0.0)
+        mexErrMsgTxt("sync_labels: labels must be a uint8 array, a RawVolume of uint8, [] or false");
+      check(vr_sync_labels(h, nullptr));
+      return;
+    }
+    if (mxGetPropertyShared(lb, 0, "TimeLastUpdate")) {  // a Volume object: the library checks its element type
+      const vr_volume v = make_volume(lb);
+      check(vr_sync_labels(h, &v));
+      return;
+    }
+    if (mxGetNumberOfElements(lb) == 0) {
+      check(vr_sync_labels(h, nullptr));
+      return;
+    }
+    if (mxGetClassID(lb) != mxUINT8_CLASS || mxIsComplex(lb) || mxGetNumberOfDimensions(lb) > 3)
+      mexErrMsgTxt("sync_labels: labels must be a uint8 array, a RawVolume of uint8, [] or false");
+    vr_volume v{};
+    v.dtype = VR_U8;
+    v.data = static_cast<const float *>(mxGetData(lb));
+    const mwSize nd = mxGetNumberOfDimensions(lb);
+    const mwSize *d = mxGetDimensions(lb);
+    v.dims[0] = d[0];
+    v.dims[1] = nd > 1 ? d[1] : 1;
+    v.dims[2] = nd > 2 ? d[2] : 1;
+    v.last_update = 0;  // a bare array has no Volume identity: uploaded by every call
+    v.location = VR_HOST;
+    check(vr_sync_labels(h, &v));
+    return;
+  }
+  if (!strcmp(cmd, "set_label_gains")) {
+    // volumeRender('set_label_gains', h, gains) (vr_set_label_gains): gains a single vector of at most 256
+    // entries, gains(l + 1) the factor of the voxels labelled l; [] or false clears the table.  The
+    // emission volume on the device follows at once; the gains stay with the handle.
+    if (nlhs > 0) mexErrMsgTxt("Too many output arguments.");
+    if (nrhs < 3) mexErrMsgTxt("insufficient parameter!");
+    if (nrhs > 3) mexErrMsgTxt("set_label_gains: too many input arguments");
+    const mxArray *g = prhs[2];
+    if (mxIsClass(g, "logical")) {
+      if (mxGetNumberOfElements(g) != 1 || mxGetScalar(g) != 0.0)
+        mexErrMsgTxt("set_label_gains: gains must be a single vector of at most 256 entries, [] or false");
+      check(vr_set_label_gains(h, nullptr, 0));
+      return;
+    }
+    if (mxGetNumberOfElements(g) == 0) {
+      check(vr_set_label_gains(h, nullptr, 0));
+      return;
+    }
+    if (mxGetClassID(g) != mxSINGLE_CLASS || mxIsComplex(g) || mxGetNumberOfDimensions(g) != 2 ||
+        (mxGetM(g) != 1 && mxGetN(g) != 1) || mxGetNumberOfElements(g) > 256)
+      mexErrMsgTxt("set_label_gains: gains must be a single vector of at most 256 entries, [] or false");
+    check(vr_set_label_gains(h, static_cast<const float *>(mxGetData(g)), (int32_t)mxGetNumberOfElements(g)));
+    return;
+  }
   mexErrMsgTxt(("Unknown command: " + std::string(cmd)).c_str());
 }

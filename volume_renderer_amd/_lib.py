@@ -25,6 +25,7 @@ VR_PROJ_MIP, VR_PROJ_SUM = 0, 1
 VR_TF_VALUE, VR_TF_DEPTH = 0, 1
 VR_TF_MAX_ENTRIES = 1024
 VR_CLIP_MAX = 6
+VR_LABEL_GAINS_MAX = 256
 # enum vr_launch_flag: the bits of vr_last_launch_flags, in bit order
 LAUNCH_FLAGS = ("tame", "small_x", "eds_finite", "skip_empty", "re_ok", "lut_ok", "tap_half", "ab_alias", "share",
                 "big", "occ")
@@ -118,6 +119,10 @@ SIGNATURES = [
     ("vr_set_clip", c_int, [c_void_p, POINTER(VrClipPlane), c_int32]),
     ("vr_get_clip", c_int, [c_void_p, POINTER(VrClipPlane), POINTER(c_int32)]),
     ("vr_clip_convert_host", c_int, [POINTER(VrClipPlane), c_int32, POINTER(c_float), POINTER(c_float), c_void_p]),
+    ("vr_sync_labels", c_int, [c_void_p, POINTER(VrVolume)]),
+    ("vr_set_label_gains", c_int, [c_void_p, c_void_p, c_int32]),
+    ("vr_get_label_gains", c_int, [c_void_p, c_void_p, POINTER(c_int32)]),
+    ("vr_label_gain_host", c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_uint64, c_void_p]),
     ("vr_partition_columns", c_int64, [c_int64, POINTER(VrPartition)]),
     ("vr_assemble_partitions", c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int64, c_void_p,
                                        c_void_p]),

@@ -31,6 +31,7 @@
 #include "../../include/vrhip.h"
 #include "vr_clip.h"
 #include "vr_device.h"
+#include "vr_labels.h"
 #include "vr_resources.h"
 #include "vr_transfer.h"
 
@@ -95,6 +96,9 @@ hipError_t launch_stats(const float *src, uint64_t n, BufStats *st, hipStream_t 
 hipError_t launch_zpair(const float *src, float *dst, uint32_t n, uint32_t pxy, hipStream_t s);
 hipError_t launch_occupancy(const float *p, uint32_t px, uint32_t py, uint32_t pz, uint8_t *occ, float inv_scale,
                             hipStream_t s);
+// vr_labels.hip: dst = src under the n gains of `gains` by the dense label bytes; *st += the statistics of dst
+hipError_t launch_label_gain(const float *src, const uint8_t *labels, const float *gains, int32_t n, int32_t nx,
+                             int32_t ny, int32_t nz, float *dst, BufStats *st, hipStream_t s);
 hipError_t launch_predict_cost(const RenderParams &P, uint32_t nb_view, uint32_t nbx, int32_t tw, int32_t th,
                                int32_t m, float dens, float xthr, uint32_t *cost, hipStream_t s);
 uint64_t interleave3_entries(uint32_t px, uint32_t py, uint32_t pz);
@@ -279,7 +283,16 @@ struct DevBuf {
   // occupancy_kernel): one byte per 8^3 brick, read by the march's empty-space probe
   uint8_t *occ = nullptr;
   uint64_t occ_bytes = 0;
+  // label gains (vr_set_label_gains): while the buffer is modulated, `orig` is the
+  // unmodified padded upload (`bytes` long) with its statistics, and ptr, nonfinite, maxabs and occ
+  // are those of the modulated values; mod_labels / mod_gains name the label upload and the gain
+  // table that ptr was derived from.  Only the label pass reads orig, and the host waits for it.
+  float *orig = nullptr;
+  bool orig_nonfinite = false;
+  float orig_maxabs = 0.f;
+  uint64_t mod_labels = 0, mod_gains = 0;
   ~DevBuf() {
+    if (orig) vr_host::pooled_free(orig, bytes, device, vr_host::Readers());
     if (zpair) vr_host::pooled_free(zpair, zpair_bytes, device, vr_host::Readers(readers));
     if (occ) vr_host::pooled_free(occ, occ_bytes, device, vr_host::Readers(readers));
     vr_host::pooled_free(ptr, bytes, device, std::move(readers));
@@ -357,6 +370,19 @@ struct vr_context {
   // clip planes (vr_set_clip), as the caller gave them; converted per launch (clip_set)
   vr_clip_plane clip[VR_CLIP_MAX] = {};
   int32_t nclip = 0;
+  // label volume and gain table (vr_sync_labels, vr_set_label_gains): the labels dense
+  // on the device, one byte per voxel, with the identity of the Volume they were uploaded from; the
+  // gains as the caller gave them and their device copy.  The versions key DevBuf::mod_labels / mod_gains.
+  uint8_t *d_labels = nullptr;
+  uint64_t labels_bytes = 0, labels_dims[3] = {0, 0, 0};
+  const void *labels_src = nullptr;
+  uint64_t labels_last_update = 0;
+  int32_t labels_location = VR_HOST;
+  uint64_t labels_version = 0;
+  float gains[VR_LABEL_GAINS_MAX] = {};
+  int32_t ngains = 0;
+  uint64_t gains_version = 0;
+  float *d_gains = nullptr;
 };
 
 namespace {
@@ -507,6 +533,13 @@ void build_occupancy(DevBuf *b, hipStream_t s) {
   VR_HIP(hipStreamSynchronize(s));
 }
 
+// Forget that b was modulated by label gains: its unmodified copy goes back to the pool (no launch reads it).
+void drop_unmodified_copy(DevBuf *b) {
+  if (b->orig) vr_host::pooled_free(b->orig, b->bytes, b->device, vr_host::Readers());
+  b->orig = nullptr;
+  b->mod_labels = b->mod_gains = 0;
+}
+
 void sync_volume(vr_context *h, int tex, int slot) {
   g_tex.bind[tex].reset();
   const VolRec &v = h->vol[slot];
@@ -520,6 +553,7 @@ void sync_volume(vr_context *h, int tex, int slot) {
     b->bytes = padded;
     if (padded) VR_HIP(vr_host::pooled_alloc(reinterpret_cast<void **>(&b->ptr), padded, h->device));
   }
+  drop_unmodified_copy(b.get());  // (the upload overwrites the modulated values: apply_labels starts afresh)
   for (int i = 0; i < 3; ++i) b->dims[i] = v.dims[i];
   b->nonfinite = false;
   b->maxabs = 0.f;
@@ -623,6 +657,9 @@ uint64_t required_memory(const vr_context *h) {
   if (!same(em, ab) && !same(re, ab)) r += ab.memory_size;
   if (!same(em, re) && !same(re, ab)) r += re.memory_size;
   r += h->vol[T_DX].memory_size + h->vol[T_DY].memory_size + h->vol[T_DZ].memory_size;
+  // label gains: the label bytes, and the unmodified copy of the emission volume while gains are set
+  r += h->labels_bytes;
+  if (h->d_labels && h->ngains > 0) r += em.memory_size;
   return r;
 }
 
@@ -672,6 +709,117 @@ void mm_sync(vr_context *h) {
     sync_volume_if_changed(h, T_DZ, T_DZ);
     g_tex.grad_method = G_LOOKUP;
   }
+}
+
+// ---- label gains (include/vrhip.h vr_sync_labels / vr_set_label_gains) ----------------
+// The buffer the handle's last sync bound as the emission texture (the slot index decides which).
+BufPtr label_target(const vr_context *h) {
+  if (!h->has_snap || h->snap_idx[0] < 0 || h->snap_idx[0] >= T_COUNT) return nullptr;
+  return h->snap_bind[h->snap_idx[0]].lock();
+}
+
+// VR_OK, or the error of label dims that differ from the dims of the resident emission buffer b.
+int check_label_dims(const uint64_t ld[3], const DevBuf *b) {
+  if (!b || !b->ptr || (ld[0] == b->dims[0] && ld[1] == b->dims[1] && ld[2] == b->dims[2])) return VR_OK;
+  std::ostringstream os;
+  os << "labels: the label volume is " << ld[0] << " x " << ld[1] << " x " << ld[2] << ", the emission volume "
+     << b->dims[0] << " x " << b->dims[1] << " x " << b->dims[2];
+  return fail(VR_ERR_ARGUMENT, os.str());
+}
+
+vr_host::Uploader &label_uploader(int device) {
+  vr_host::Uploader &U = vr_host::uploaders()[device];
+  VR_HIP(U.init(device));
+  return U;
+}
+
+// b holds its unmodified upload again, with that upload's statistics and occupancy map.
+void restore_unmodified(DevBuf *b) {
+  if (!b->orig) return;
+  b->readers.wait();  // launches in flight read ptr and occ
+  vr_host::pooled_free(b->ptr, b->bytes, b->device, vr_host::Readers());
+  b->ptr = b->orig;
+  b->orig = nullptr;
+  b->nonfinite = b->orig_nonfinite;
+  b->maxabs = b->orig_maxabs;
+  b->mod_labels = b->mod_gains = 0;
+  b->version = next_version();
+  build_occupancy(b, label_uploader(b->device).pad_stream);
+}
+
+// Bring the handle's emission buffer up to date with its labels and gains: modulated when emission,
+// labels and n > 0 are all present, unmodified otherwise; nothing is written when nothing changed.
+// The first modulation of an upload takes a second buffer and swaps: the upload becomes the
+// unmodified copy, the pass writes the new ptr (no copy of the volume).  The state left is that of an
+// upload of the host-rewritten volume: data and apron, statistics, occupancy map, a new version.
+int apply_labels(vr_context *h) {
+  BufPtr b = label_target(h);
+  if (!b || !b->ptr) return VR_OK;
+  const bool want = h->d_labels && h->ngains > 0;
+  const int bad = want ? check_label_dims(h->labels_dims, b.get()) : VR_OK;
+  if (!want || bad) {
+    restore_unmodified(b.get());
+    return bad;
+  }
+  if (b->orig && b->mod_labels == h->labels_version && b->mod_gains == h->gains_version) return VR_OK;
+  vr_host::Uploader &U = label_uploader(b->device);
+  if (!h->d_gains)
+    VR_HIP(vr_host::device_alloc(reinterpret_cast<void **>(&h->d_gains), sizeof(h->gains)));
+  b->readers.wait();  // "neither rewritten nor freed before all of them": renders in flight keep their gains
+  if (!b->orig) {
+    float *fresh = nullptr;
+    VR_HIP(vr_host::pooled_alloc(reinterpret_cast<void **>(&fresh), b->bytes, b->device));
+    b->orig = b->ptr;
+    b->ptr = fresh;
+    b->orig_nonfinite = b->nonfinite;
+    b->orig_maxabs = b->maxabs;
+  }
+  b->mod_labels = b->mod_gains = 0;  // (until the pass below has completed)
+  try {
+    VR_HIP(hipMemcpy(h->d_gains, h->gains, sizeof(float) * (size_t)h->ngains, hipMemcpyHostToDevice));
+    VR_HIP(hipMemsetAsync(U.d_stats, 0, sizeof(vr::BufStats), U.pad_stream));
+    VR_HIP(vr::launch_label_gain(b->orig, h->d_labels, h->d_gains, h->ngains, (int32_t)b->dims[0], (int32_t)b->dims[1],
+                                 (int32_t)b->dims[2], b->ptr, U.d_stats, U.pad_stream));
+    VR_HIP(hipMemcpyAsync(U.h_stats, U.d_stats, sizeof(vr::BufStats), hipMemcpyDeviceToHost, U.pad_stream));
+    VR_HIP(hipStreamSynchronize(U.pad_stream));
+    b->nonfinite = U.h_stats->nonfinite != 0;
+    b->maxabs = U.h_stats->maxabs;
+    b->version = next_version();
+    build_occupancy(b.get(), U.pad_stream);
+  } catch (...) {  // the buffer must not stay half written: back to the unmodified upload
+    vr_host::pooled_free(b->ptr, b->bytes, b->device, vr_host::Readers());
+    b->ptr = b->orig;
+    b->orig = nullptr;
+    b->nonfinite = b->orig_nonfinite;
+    b->maxabs = b->orig_maxabs;
+    b->version = next_version();
+    throw;
+  }
+  b->mod_labels = h->labels_version;
+  b->mod_gains = h->gains_version;
+  return VR_OK;
+}
+
+void free_labels(vr_context *h) {
+  if (h->d_labels) (void)hipFree(h->d_labels);
+  h->d_labels = nullptr;
+  h->labels_bytes = 0;
+  h->labels_src = nullptr;
+  h->labels_last_update = 0;
+  for (uint64_t &d : h->labels_dims) d = 0;
+}
+
+int labels_unsupported(const char *what) {
+  return fail(VR_ERR_UNSUPPORTED, std::string(what) + ": labels and label gains are not supported on a multi-device "
+                                                      "group handle");
+}
+
+int check_label_gains(const float *gains, int32_t n) {
+  if (n < 0 || n > VR_LABEL_GAINS_MAX) return fail(VR_ERR_ARGUMENT, "label gains: n must be in 0..256");
+  if (n > 0 && !gains) return fail(VR_ERR_ARGUMENT, "label gains: gains is NULL");
+  for (int32_t i = 0; i < n; ++i)
+    if (!std::isfinite(gains[i])) return fail(VR_ERR_ARGUMENT, "label gains: every gain must be finite");
+  return VR_OK;
 }
 
 vr::DevTex dev_tex(const BufPtr &b) {
@@ -2471,6 +2619,12 @@ int vr_delete(vr_context *h) {
   for (hipEvent_t e : h->tev)
     if (e) (void)hipEventDestroy(e);
   if (h->d_part) (void)hipFree(h->d_part);
+  {  // the handle's label bytes and gain table (the unmodified copies went with the buffers above)
+    DeviceGuard dl(h->device);
+    free_labels(h);
+    if (h->d_gains) (void)hipFree(h->d_gains);
+    h->d_gains = nullptr;
+  }
   g_contexts.erase(h);
   h->signature = 0;
   delete h;
@@ -2507,6 +2661,9 @@ int vr_mem_info(vr_context *h, char *buf, size_t buflen) {
      << "\t\tdY (MB): " << mb(h->vol[T_DY].memory_size) << " ptr: " << ptr(T_DY) << "\n"
      << "\t\tdZ (MB): " << mb(h->vol[T_DZ].memory_size) << " ptr: " << ptr(T_DZ) << "\n"
      << "\t\tlight (MB): " << mb(h->vol[T_LIGHT].memory_size) << " ptr: " << ptr(T_LIGHT) << "\n"
+     << "\t\tlabels (MB): " << mb(h->labels_bytes) << " ptr: " << (const void *)h->d_labels
+     << ", label gains: " << h->ngains << ", unmodified emission copy (MB): "
+     << mb(label_target(h) && label_target(h)->orig ? label_target(h)->bytes : 0) << "\n"
      << "\t\treusable buffers (MB): " << mb(vr_host::pool_bytes(h->device)) << "\n\n"
      << "\t\tSimilarity of Volumes\n\t\t---------------------\n"
      << "\t\t\tEm\tAb\tRe\n"
@@ -2618,7 +2775,7 @@ static int do_sync_volumes(vr_context *h, uint64_t time_last_mem_sync, const vr_
   h->snap_idx[2] = g_tex.idx_re;
   h->snap_grad = g_tex.grad_method;
   h->has_snap = true;
-  return VR_OK;
+  return apply_labels(h);  // label gains: the freshly bound emission buffer follows the handle's table
   VR_GUARD_END
 }
 
@@ -3126,6 +3283,99 @@ int vr_get_clip(vr_context *h, vr_clip_plane *planes, int32_t *n) {
   if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
   for (int32_t i = 0; i < h->nclip; ++i) planes[i] = h->clip[i];
   *n = h->nclip;
+  return VR_OK;
+}
+
+int vr_sync_labels(vr_context *h, const vr_volume *labels) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  uint64_t count = 0;
+  if (labels) {
+    if (labels->dtype != VR_U8)
+      return fail(VR_ERR_ARGUMENT, "labels: the label volume must be uint8 (VR_U8 without VR_DTYPE_UNORM)");
+    if (labels->location != VR_HOST && labels->location != VR_DEVICE)
+      return fail(VR_ERR_ARGUMENT, "labels: invalid location");
+    if (labels->dims[0] > 0x7FFFFFFF || labels->dims[1] > 0x7FFFFFFF || labels->dims[2] > 0x7FFFFFFF)
+      return fail(VR_ERR_UNSUPPORTED, "labels: volume dimension too large");
+    count = labels->dims[0] * labels->dims[1] * labels->dims[2];
+    if (count && !labels->data) return fail(VR_ERR_ARGUMENT, "labels: volume data is NULL");
+  }
+  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
+  if (!h->children.empty()) return labels_unsupported("vr_sync_labels");
+  VR_GUARD_BEGIN
+  DeviceGuard dg(h->device);
+  vr_host::prune_retired();
+  if (!count) {  // NULL (or an empty volume) drops them
+    if (h->d_labels) h->labels_version = next_version();
+    free_labels(h);
+    return apply_labels(h);
+  }
+  const BufPtr b = label_target(h);
+  if (h->ngains > 0)
+    if (int rc = check_label_dims(labels->dims, b.get())) return rc;  // (the old labels stay)
+  // the same Volume identity (data pointer, TimeLastUpdate, size) is not uploaded again, as the LUT's
+  const bool same_volume = h->d_labels && h->labels_src == labels->data && h->labels_last_update == labels->last_update &&
+                           h->labels_location == labels->location && labels->last_update != 0 &&
+                           h->labels_dims[0] == labels->dims[0] && h->labels_dims[1] == labels->dims[1] &&
+                           h->labels_dims[2] == labels->dims[2] && !env_flag("VR_ALWAYS_REUPLOAD");
+  if (!same_volume) {
+    if (h->labels_bytes != count) {
+      const bool copy = h->ngains > 0 && b && b->ptr && !b->orig;
+      if (int rc = check_free_device_memory(count + (copy ? b->bytes : 0))) return rc;
+      free_labels(h);
+      VR_HIP(vr_host::device_alloc(reinterpret_cast<void **>(&h->d_labels), count));
+      h->labels_bytes = count;
+    }
+    // (no label pass is in flight: apply_labels waits for its own.)  Device data is read after the work
+    // already queued on the null stream, as the upload path reads a device volume.
+    const bool dev = labels->location == VR_DEVICE;
+    VR_HIP(hipMemcpy(h->d_labels, labels->data, count, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    if (dev) VR_HIP(hipStreamSynchronize(nullptr));
+    for (int i = 0; i < 3; ++i) h->labels_dims[i] = labels->dims[i];
+    h->labels_src = labels->data;
+    h->labels_last_update = labels->last_update;
+    h->labels_location = labels->location;
+    h->labels_version = next_version();
+  }
+  return apply_labels(h);
+  VR_GUARD_END
+}
+
+int vr_set_label_gains(vr_context *h, const float *gains, int32_t n) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (int rc = check_label_gains(gains, n)) return rc;
+  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
+  if (n > 0 && !h->children.empty()) return labels_unsupported("vr_set_label_gains");
+  if (n == h->ngains && (n == 0 || !std::memcmp(gains, h->gains, sizeof(float) * (size_t)n))) return VR_OK;  // no change
+  VR_GUARD_BEGIN
+  DeviceGuard dg(h->device);
+  vr_host::prune_retired();
+  const BufPtr b = label_target(h);
+  if (n > 0 && h->d_labels) {
+    if (int rc = check_label_dims(h->labels_dims, b.get())) return rc;  // (the old table stays)
+    if (b && b->ptr && !b->orig)
+      if (int rc = check_free_device_memory(b->bytes)) return rc;
+  }
+  for (int32_t i = 0; i < n; ++i) h->gains[i] = gains[i];
+  h->ngains = n;
+  h->gains_version = next_version();
+  return apply_labels(h);
+  VR_GUARD_END
+}
+
+int vr_get_label_gains(vr_context *h, float *gains, int32_t *n) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!gains || !n) return fail(VR_ERR_ARGUMENT, "label gains: gains / n is NULL");
+  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
+  for (int32_t i = 0; i < h->ngains; ++i) gains[i] = h->gains[i];
+  *n = h->ngains;
+  return VR_OK;
+}
+
+int vr_label_gain_host(const float *src, const uint8_t *labels, const float *gains, int32_t n, uint64_t count,
+                       float *dst) {
+  if (int rc = check_label_gains(gains, n)) return rc;
+  if (count && (!src || !dst || (n > 0 && !labels))) return fail(VR_ERR_ARGUMENT, "label gains: src / labels / dst is NULL");
+  for (uint64_t i = 0; i < count; ++i) dst[i] = vr_label_gain(src[i], n > 0 ? labels[i] : 0u, gains, n);
   return VR_OK;
 }
 

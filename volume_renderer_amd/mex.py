@@ -444,6 +444,86 @@ def clip_convert_host(planes, bmin, bscale) -> np.ndarray:
     return out
 
 
+def label_volume(labels):
+    """The vr_volume of a label volume: a uint8 array (column-major; no Volume identity, so it is
+    uploaded by every call), a RawVolume of uint8 or a DeviceVolume of uint8 (their TimeLastUpdate
+    spares a repeated upload); None, False or an empty array: no labels.  Returns (VrVolume or None,
+    keep-alive); the library checks the element type."""
+    if labels is None or _is_false(labels):
+        return None, None
+    if isinstance(labels, DeviceVolume) or hasattr(labels, "TimeLastUpdate"):
+        v = _vr_volume(labels)
+        return (v if v.dims[0] * v.dims[1] * v.dims[2] else None), labels
+    a = np.asarray(labels)
+    if a.size == 0:
+        return None, None
+    if a.dtype != np.uint8:
+        raise _lib.VrError(1, "sync_labels: labels must be a uint8 array, a RawVolume of uint8, [] or false")
+    if a.ndim > 3:
+        raise _lib.VrError(1, "sync_labels: labels must have at most 3 dimensions")
+    a = np.asfortranarray(a)
+    v = VrVolume()
+    v.data = a.ctypes.data
+    for i, d in enumerate(_matlab_dims(a)):
+        v.dims[i] = d
+    v.last_update = 0
+    v.location = _lib.VR_HOST
+    v.dtype = _lib.VR_U8
+    return v, a
+
+
+def sync_labels(handle, labels) -> None:
+    """vr_sync_labels: the handle's label volume (label_volume(); None / False / [] drops it)."""
+    v, keep = label_volume(labels)
+    check(lib().vr_sync_labels(_handle(handle), ctypes.byref(v) if v is not None else None))
+    del keep
+
+
+def label_gains(gains):
+    """A gain table as a contiguous single vector (None, False or empty: no gains).  Returns (array or
+    None, n); the library checks the count and the values."""
+    if gains is None or _is_false(gains):
+        return None, 0
+    a = np.asarray(gains)
+    if a.size == 0:
+        return None, 0
+    if a.dtype.kind not in "fiu" or a.size != max(a.shape, default=0):
+        raise _lib.VrError(1, "set_label_gains: gains must be a real vector of at most 256 entries, [] or false")
+    a = np.ascontiguousarray(a.reshape(-1), dtype=np.float32)
+    return a, int(a.size)
+
+
+def set_label_gains(handle, gains) -> None:
+    """vr_set_label_gains: replace the handle's gain table, one fp32 gain per label (label_gains();
+    None / False / [] clears it)."""
+    a, n = label_gains(gains)
+    check(lib().vr_set_label_gains(_handle(handle), a.ctypes.data if a is not None else None, n))
+
+
+def get_label_gains(handle) -> np.ndarray:
+    """vr_get_label_gains: the handle's gain table as set, [n] single (empty: none)."""
+    out = np.zeros(_lib.VR_LABEL_GAINS_MAX, np.float32)
+    n = ctypes.c_int32(0)
+    check(lib().vr_get_label_gains(_handle(handle), out.ctypes.data, ctypes.byref(n)))
+    return out[:n.value].copy()
+
+
+def label_gain_host(src, labels, gains) -> np.ndarray:
+    """vr_label_gain_host: the label pass's value rule on the CPU -- src single, labels uint8 of the same
+    shape, gains as label_gains(); returns labels < n ? src * gains[labels] : src, shaped like src."""
+    s = np.asarray(src, dtype=np.float32)
+    l = np.asarray(labels, dtype=np.uint8)
+    if l.shape != s.shape:
+        raise _lib.VrError(1, "label_gain_host: src and labels differ in shape")
+    sf = np.ascontiguousarray(s.reshape(-1, order="F"))
+    lf = np.ascontiguousarray(l.reshape(-1, order="F"))
+    a, n = label_gains(gains)
+    out = np.empty(sf.size, np.float32)
+    check(lib().vr_label_gain_host(sf.ctypes.data, lf.ctypes.data, a.ctypes.data if a is not None else None, n, sf.size,
+                                   out.ctypes.data))
+    return out.reshape(s.shape, order="F")
+
+
 def set_option(name: str, value: int) -> None:
     """vr_set_option: a process-wide library option (include/vrhip.h)."""
     check(lib().vr_set_option(name.encode(), int(value)))
@@ -590,7 +670,7 @@ def _group_devices():
 def volumeRender(cmd, *args):
     """The `volumeRender` mex: commands 'new', 'delete', 'mem_info', 'sync_volumes', 'render' (and
     'render_stereo', 'render_channels', 'render_projection', 'render_isosurface', 'render_transfer',
-    'set_clip', which the reference does not have)."""
+    'set_clip', 'sync_labels', 'set_label_gains', which the reference does not have)."""
     nrhs = 1 + len(args)
     if not isinstance(cmd, str) or len(cmd) >= 64:
         raise _lib.VrError(1, "First input should be a command string less than 64 characters long.")
@@ -649,6 +729,30 @@ def volumeRender(cmd, *args):
             pl = pl.T
         arr, n = clip_planes(pl)
         check(L.vr_set_clip(h, arr, n))
+        return None
+    if cmd == "sync_labels":  # ('sync_labels', h, labels): a uint8 array or a RawVolume of uint8; [] / false drops
+        if nrhs < 3:
+            raise _lib.VrError(1, "insufficient parameter!")
+        if nrhs > 3:
+            raise _lib.VrError(1, "sync_labels: too many input arguments")
+        lb = args[1]
+        if isinstance(lb, (bool, np.bool_)) and bool(lb):
+            raise _lib.VrError(1, "sync_labels: labels must be a uint8 array, a RawVolume of uint8, [] or false")
+        sync_labels(args[0], lb)
+        return None
+    if cmd == "set_label_gains":  # ('set_label_gains', h, gains): a single vector of at most 256 entries; [] / false clears
+        if nrhs < 3:
+            raise _lib.VrError(1, "insufficient parameter!")
+        if nrhs > 3:
+            raise _lib.VrError(1, "set_label_gains: too many input arguments")
+        g = args[1]
+        if not (g is None or _is_false(g)):
+            g = np.asarray(g)
+            if g.size and (g.dtype != np.float32 or g.size != max(g.shape, default=0)):
+                raise _lib.VrError(1, "set_label_gains: gains must be a single vector of at most 256 entries, [] or false")
+            if g.size > _lib.VR_LABEL_GAINS_MAX:
+                raise _lib.VrError(1, "set_label_gains: gains must be a single vector of at most 256 entries, [] or false")
+        set_label_gains(args[0], g)
         return None
     if cmd == "render_stereo":  # fused stereo pair (vr_render_stereo): args as 'render' + base
         ra, keep = render_args(*args[1:10])

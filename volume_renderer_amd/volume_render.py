@@ -86,6 +86,15 @@ class VolumeRender:
         # handle before a render whenever they differ from what it holds (_apply_clip).
         self.ClipPlanes = np.zeros((0, 4), dtype=np.float32)
         object.__setattr__(self, "_clip_applied", np.zeros((0, 4), dtype=np.float32))
+        # label volume and gain table (vr_sync_labels, vr_set_label_gains): VolumeLabels a uint8 array of
+        # the size of VolumeEmission.Data, a RawVolume of uint8 or a DeviceVolume of uint8 (False: none),
+        # LabelGains one gain per label (empty: none) -- the emission volume on the device is
+        # VolumeEmission.Data times LabelGains[VolumeLabels], without another upload.  Sent to the
+        # handle before a render whenever they changed (_apply_labels).
+        self.VolumeLabels = False
+        self.LabelGains = np.zeros(0, dtype=np.float32)
+        object.__setattr__(self, "_labels_applied", None)  # what the handle holds: None, no labels
+        object.__setattr__(self, "_gains_applied", np.zeros(0, dtype=np.float32))
         if VolumeRender._default_reflection is None:
             VolumeRender._default_reflection = Volume(1)
         # observable properties: defaults are assigned without firing the listener
@@ -127,6 +136,26 @@ class VolumeRender:
                 val = val.reshape(1, 4)
             if val.ndim != 2 or val.shape[1] != 4:
                 raise TypeError("ClipPlanes must be an n x 4 matrix with rows [n0 n1 n2 offset]")
+        elif name == "VolumeLabels":
+            if val is None or _is_logical(val):
+                if val:
+                    raise TypeError("VolumeLabels must be a uint8 array, a RawVolume of uint8, a DeviceVolume or False")
+                val = False
+            elif not hasattr(val, "TimeLastUpdate"):
+                val = np.asarray(val)
+                if val.size == 0:
+                    val = False
+                elif val.dtype != np.uint8 or val.ndim > 3:
+                    raise TypeError("VolumeLabels must be a uint8 array, a RawVolume of uint8, a DeviceVolume or False")
+                else:
+                    val = np.asfortranarray(val)
+            if val is not False or getattr(self, "_labels_applied", None) is not None:
+                object.__setattr__(self, "_labels_applied", "assigned")  # an assignment is a change
+        elif name == "LabelGains":
+            val = np.zeros(0, np.float32) if val is None or _is_logical(val) else np.asarray(val, dtype=np.float32)
+            if val.size != max(val.shape, default=0) or val.size > 256:
+                raise TypeError("LabelGains must be a vector of at most 256 gains")
+            val = val.reshape(-1).copy()
         object.__setattr__(self, name, val)
         if name in _VOLUME_PROPS and isinstance(val, Volume):
             val.TimeLastUpdate = timestamp()
@@ -159,6 +188,18 @@ class VolumeRender:
         if not np.array_equal(self.ClipPlanes, self._clip_applied):
             volumeRender("set_clip", self.objectHandle, np.asfortranarray(self.ClipPlanes.T))
             object.__setattr__(self, "_clip_applied", self.ClipPlanes.copy())
+
+    def _apply_labels(self) -> None:
+        """'sync_labels' if VolumeLabels changed since the last one (assigned, or a Volume's
+        TimeLastUpdate moved), 'set_label_gains' if LabelGains differs from what the handle holds."""
+        lb = self.VolumeLabels
+        key = None if lb is False else (id(lb), int(lb.TimeLastUpdate) if hasattr(lb, "TimeLastUpdate") else None)
+        if key != self._labels_applied:
+            volumeRender("sync_labels", self.objectHandle, lb)
+            object.__setattr__(self, "_labels_applied", key)
+        if not np.array_equal(self.LabelGains, self._gains_applied):
+            volumeRender("set_label_gains", self.objectHandle, self.LabelGains)
+            object.__setattr__(self, "_gains_applied", self.LabelGains.copy())
 
     def memInfo(self) -> None:
         volumeRender("mem_info", self.objectHandle)
@@ -219,6 +260,7 @@ class VolumeRender:
         """Validate and sync the volumes as _p_render does, then 'render_projection'."""
         self._validate_volumes()
         self._apply_clip()
+        self._apply_labels()
         self.syncVolumes()
         return volumeRender("render_projection", self.objectHandle, *self._render_argv(camera_x_offset, resolution),
                             mode)
@@ -247,6 +289,7 @@ class VolumeRender:
         render arguments), then 'render_isosurface'."""
         self._validate_volumes()
         self._apply_clip()
+        self._apply_labels()
         self.syncVolumes()
         return volumeRender("render_isosurface", self.objectHandle, *self._render_argv(camera_x_offset, resolution),
                             level)
@@ -278,6 +321,7 @@ class VolumeRender:
         render arguments), then 'render_transfer'."""
         self._validate_volumes()
         self._apply_clip()
+        self._apply_labels()
         self.syncVolumes()
         cm = np.asfortranarray(colormap, dtype=np.float32)
         am = False if alphamap is None else np.asarray(alphamap, dtype=np.float32).reshape(-1, 1)
@@ -327,6 +371,7 @@ class VolumeRender:
         for r in renders:
             with_grads = r._validate_volumes()
             r._apply_clip()  # (a channel with planes: the library answers VR_ERR_UNSUPPORTED)
+            r._apply_labels()
             argv = r._render_argv(np.float32(-base if stereo else 0.0), resolution)
             vols = [r.VolumeEmission, r.VolumeReflection, r.VolumeAbsorption]
             if with_grads:
@@ -379,6 +424,7 @@ class VolumeRender:
                 raise ValueError("All gradient dimensions need to be set and of type Volume!")
             with_grads = True
         self._apply_clip()
+        self._apply_labels()
         self.syncVolumes()
         factors = np.array([self.FactorEmission, self.FactorReflection, self.FactorAbsorption])
         props = np.array([camera_x_offset, self.FocalLength, self.DistanceToObject], dtype=np.float64)
