@@ -484,6 +484,91 @@ int vr_get_label_gains(vr_context *h, float *gains /* 256 */, int32_t *n);
 int vr_label_gain_host(const float *src, const uint8_t *labels, const float *gains, int32_t n, uint64_t count,
                        float *dst);
 
+/* --- slice views: axis-aligned, oblique and thick-slab sections of a resident volume (no reference
+ * counterpart; MATLAB's sliceViewer / obliqueslice, a radiologist's MPR) ------------------------------
+ * The sampler of every render evaluated on a plane instead of along camera rays: what the renderer shows
+ * -- typed uploads widened, label gains applied -- not what the host array holds.  No camera is involved.
+ * Coordinates.  q is the normalized volume coordinate in the dimension order of Data, exactly the
+ * coordinate of the clip planes (q_j from 0 to 1 across dims[j], the centre of voxel i at (i + 0.5) / d_j):
+ * the sampler's own argument.  Sample k of the pixel in row y, column x, in fp32 with every operation
+ * rounded once:
+ *   p_j  = fmaf(dv_j, (float)y, fmaf(du_j, (float)x, origin_j));
+ *   q_kj = fmaf(dw_j, (float)k, p_j)
+ * -- no recurrence, so no bit depends on how the kernel orders or batches the samples.  A sample is inside
+ * iff q_kj >= 0 && q_kj <= 1 for j = 0, 1, 2 (a NaN coordinate is outside).  Outside samples are skipped,
+ * not clamped.  An inside sample is v_k = tex3d(source texture, q_k0, q_k1, q_k2) with the clamp addressing
+ * and the 8-bit weights of every other render.
+ * Source.  The texture a 'render' on this handle would sample as emission, absorption or reflection: the
+ * slot indices, the alias rule and the module-global bindings included (the last vr_sync_volumes on any
+ * handle decides what is bound; as in 'render', the absorption index follows the reference: it points at
+ * the emission texture unless the alias rule moved it, also after a separate absorption volume was
+ * synced); an unbound texture reads 0, a 1x1x1 texture gives its voxel through the lerp algebra.  The emission source is the resident buffer: label gains show, a typed upload shows as
+ * widened.  Clip planes set on the handle are ignored: the slice is itself the cut.
+ * Reduction over k = 0 .. n-1, in this order:
+ *   VR_SLICE_MAX  m = -inf; an inside sample with v_k > m (strictly: the first maximum wins, a NaN never
+ *                 does) sets m = v_k, kk = k.  pixel = m + 0.0f (-0 becomes +0), aux = (float)kk; with no
+ *                 winner both are NaN.
+ *   VR_SLICE_MIN  the mirror image: m = +inf, v_k < m.
+ *   VR_SLICE_SUM  s = 0, c = 0; per inside sample s = s + v_k (one fp32 addition each) and ++c.
+ *                 pixel = c > 0 ? s : NaN, aux = (float)c (the mean is pixel ./ aux).
+ *   label plane   at the centre sample kc = (n - 1) / 2 (integer division): if it is inside and labels
+ *                 are resident (vr_sync_labels), (float)labels[i0 + D0 * (i1 + D1 * i2)] with
+ *                 i_j = min((int)(q_j * (float)D_j), D_j - 1), D the label volume's own dims; otherwise
+ *                 NaN.  Without labels the whole plane is NaN.
+ * Outputs.  Planes [H, W] column-major (out[x * H + y]) like the projections' aux plane; out_aux and
+ * out_labels may be NULL.
+ * Errors, checked before the handle (no device needed), each VR_ERR_ARGUMENT: s NULL; a non-finite
+ * component of origin / du / dv / dw; samples outside 1 .. VR_SLICE_MAX_SAMPLES; an unknown mode or source;
+ * H * W >= 2^31.  A NULL out / d_out with a non-empty image is VR_ERR_ARGUMENT; a multi-device group
+ * handle is VR_ERR_UNSUPPORTED.  The call writes nothing of the handle's state: a 'render' before and
+ * after it gives the same bits.  The device variant is asynchronous on `stream` and registers its reads
+ * like the other *_device calls: a label-gain rewrite waits for it, so a slice in flight shows the gains
+ * that were set when it was launched.  VR_SLICE_LANES=x|y (a test switch) forces which output axis runs
+ * along a wave's lanes; no bit depends on it. */
+enum vr_slice_mode { VR_SLICE_MAX = 0, VR_SLICE_MIN = 1, VR_SLICE_SUM = 2 };
+enum vr_slice_source { VR_SLICE_EMISSION = 0, VR_SLICE_ABSORPTION = 1, VR_SLICE_REFLECTION = 2 };
+#define VR_SLICE_MAX_SAMPLES 4096
+typedef struct vr_slice {
+  float origin[3];        /* q of output pixel (row 0, column 0), slab sample 0 */
+  float du[3];            /* q step per output column x */
+  float dv[3];            /* q step per output row y    */
+  float dw[3];            /* q step per slab sample k   */
+  uint64_t resolution[2]; /* [H W], as vr_render_args.resolution */
+  int32_t samples;        /* n, 1 .. VR_SLICE_MAX_SAMPLES; 1 = a plain slice */
+  int32_t mode;           /* vr_slice_mode */
+  int32_t source;         /* vr_slice_source */
+  int32_t reserved;
+} vr_slice;
+
+/* Into the caller-owned host planes out[H*W] and, where not NULL, out_aux[H*W], out_labels[H*W]. */
+int vr_render_slice(vr_context *h, const vr_slice *s, float *out, float *out_aux, float *out_labels);
+
+/* Into device memory on `stream` (asynchronous, as vr_render_device). */
+int vr_render_slice_device(vr_context *h, const vr_slice *s, float *d_out, float *d_aux, float *d_labels,
+                           void *stream);
+
+/* Two host helpers that fill in a vr_slice's geometry and samples (mode, source and reserved are left as
+ * they are); they need no device.  Everything is computed in double and rounded once to fp32.
+ * vr_slice_axis: the voxel plane at 0-based `index` (fractions allowed) along `axis` (0, 1, 2) of a volume
+ * of `dims`, one output pixel per voxel at the voxel centres: with (a, b) the two remaining dimensions,
+ * a < b, rows run along a (H = dims[a], dv_a = 1 / dims[a]) and columns along b (W = dims[b]); the slab
+ * of `thickness` samples one voxel apart is centred on `index`: sample k at voxel index
+ * index - (thickness - 1) / 2 + k along `axis`.  VR_ERR_ARGUMENT: dims or out NULL, a zero dim, an axis
+ * outside 0..2, a non-finite index, a thickness outside 1 .. VR_SLICE_MAX_SAMPLES.
+ * vr_slice_oblique: an H x W plane through point_q (the image centre, (H - 1) / 2 and (W - 1) / 2, of the
+ * slab's middle (thickness - 1) / 2) that is orthonormal in physical space: with the physical position
+ * of q along dims[j] being q_j * dims[j] * element_size_um[2 - j] (element_size_um in MATLAB order, as in
+ * vr_render_args), w = normal / |normal|, the row direction v = up projected into the plane, normalized,
+ * the column direction u = v x w; pixels pixel_um apart in the plane and slab samples pixel_um apart along
+ * w.  normal_um and up_um are physical directions with component j along dims[j].  VR_ERR_ARGUMENT: a
+ * NULL pointer, a zero dim, a non-positive or non-finite element size or pixel_um, non-finite inputs, a
+ * zero normal, an up parallel to the normal (or zero), H * W >= 2^31, thickness outside
+ * 1 .. VR_SLICE_MAX_SAMPLES. */
+int vr_slice_axis(const uint64_t dims[3], int32_t axis, double index, uint64_t thickness, vr_slice *out);
+int vr_slice_oblique(const uint64_t dims[3], const float element_size_um[3], const double point_q[3],
+                     const double normal_um[3], const double up_um[3], double pixel_um, uint64_t H, uint64_t W,
+                     uint64_t thickness, vr_slice *out);
+
 /* The kernel's table lookup on the CPU (needs no device): out[k * m + j] = L(table plane k, n, lim,
  * c[j]) for the ncomp planes table[k * n + i].  VR_ERR_ARGUMENT for a NULL pointer with m > 0, an n
  * outside 2..VR_TF_MAX_ENTRIES, ncomp < 1, or limits that are not finite with lo < hi. */

@@ -264,6 +264,62 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     if (nlhs > 1) plhs[1] = aux; else mxDestroyArray(aux);
     return;
   }
+  if (!strcmp(cmd, "render_slice")) {
+    // volumeRender('render_slice', h, geom, res, n, mode, source) -> [img, aux, labels] (vr_render_slice):
+    // geom single 3 x 4 [origin du dv dw] in the normalized volume coordinate (dimension order of Data),
+    // res uint64 [H W], n slab samples, mode 'max' | 'min' | 'sum', source 'emission' | 'absorption' |
+    // 'reflection' (or their codes); aux [H W] the index of the extremum resp. the count of inside samples,
+    // labels [H W] the label at the slab's centre sample (NaN: outside, or no labels resident)
+    if (nlhs > 3) mexErrMsgTxt("Too many output arguments.");
+    if (nrhs < 7) mexErrMsgTxt("insufficient parameter!");
+    if (nrhs > 7) mexErrMsgTxt("render_slice: too many input arguments");
+    const mxArray *g = prhs[2];
+    if (mxGetClassID(g) != mxSINGLE_CLASS || mxIsComplex(g) || mxGetNumberOfDimensions(g) != 2 || mxGetM(g) != 3 ||
+        mxGetN(g) != 4)
+      mexErrMsgTxt("render_slice: geom must be a single 3 x 4 matrix [origin du dv dw]");
+    if (mxGetClassID(prhs[3]) != mxUINT64_CLASS || mxGetNumberOfElements(prhs[3]) != 2)
+      mexErrMsgTxt("render_slice: res must be uint64 [H W]");
+    vr_slice s{};
+    const float *gd = static_cast<const float *>(mxGetData(g));
+    memcpy(s.origin, gd, sizeof(s.origin));
+    memcpy(s.du, gd + 3, sizeof(s.du));
+    memcpy(s.dv, gd + 6, sizeof(s.dv));
+    memcpy(s.dw, gd + 9, sizeof(s.dw));
+    memcpy(s.resolution, mxGetData(prhs[3]), sizeof(s.resolution));
+    if (mxGetNumberOfElements(prhs[4]) != 1 || mxIsComplex(prhs[4])) mexErrMsgTxt("render_slice: n must be a real scalar");
+    const double n = mxGetScalar(prhs[4]);
+    s.samples = (n >= 1.0 && n <= (double)VR_SLICE_MAX_SAMPLES && n == (double)(int32_t)n) ? (int32_t)n : 0;  // (0: refused below)
+    // a name or a code; an unknown name becomes the invalid code -1, which the library refuses
+    auto code = [](const mxArray *a, const char *const *names, int count, const char *what) -> int32_t {
+      char buf[16];
+      if (mxGetClassID(a) == mxCHAR_CLASS) {
+        if (mxGetString(a, buf, sizeof(buf))) return -1;
+        for (int i = 0; i < count; ++i)
+          if (!strcmp(buf, names[i])) return i;
+        return -1;
+      }
+      if (mxGetNumberOfElements(a) != 1 || mxIsComplex(a)) mexErrMsgTxt(what);
+      const double v = mxGetScalar(a);
+      return (v >= 0.0 && v < (double)count && v == (double)(int32_t)v) ? (int32_t)v : -1;
+    };
+    static const char *const modes[3] = {"max", "min", "sum"};
+    static const char *const sources[3] = {"emission", "absorption", "reflection"};
+    s.mode = code(prhs[5], modes, 3, "render_slice: mode must be 'max', 'min', 'sum' or a code");
+    s.source = code(prhs[6], sources, 3, "render_slice: source must be 'emission', 'absorption', 'reflection' or a code");
+    if (s.resolution[0] > 0x7FFFFFFFull || s.resolution[1] > 0x7FFFFFFFull ||
+        s.resolution[0] * s.resolution[1] >= (1ull << 31))
+      check(vr_render_slice(h, &s, nullptr, nullptr, nullptr));  // (refused before the handle, with its message)
+    const mwSize H = (mwSize)s.resolution[0], W = (mwSize)s.resolution[1];
+    mxArray *img = mxCreateNumericMatrix(H, W, mxSINGLE_CLASS, mxREAL);
+    mxArray *aux = mxCreateNumericMatrix(H, W, mxSINGLE_CLASS, mxREAL);
+    mxArray *lab = mxCreateNumericMatrix(H, W, mxSINGLE_CLASS, mxREAL);
+    check(vr_render_slice(h, &s, static_cast<float *>(mxGetData(img)), static_cast<float *>(mxGetData(aux)),
+                          static_cast<float *>(mxGetData(lab))));
+    plhs[0] = img;
+    if (nlhs > 1) plhs[1] = aux; else mxDestroyArray(aux);
+    if (nlhs > 2) plhs[2] = lab; else mxDestroyArray(lab);
+    return;
+  }
   if (!strcmp(cmd, "render_isosurface")) {
     // volumeRender('render_isosurface', h, <render args>, level) -> [img, depth, normal]
     // (vr_render_isosurface): the first-hit surface emission == level lit by the lights, the depth of

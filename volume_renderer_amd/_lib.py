@@ -26,6 +26,10 @@ VR_TF_VALUE, VR_TF_DEPTH = 0, 1
 VR_TF_MAX_ENTRIES = 1024
 VR_CLIP_MAX = 6
 VR_LABEL_GAINS_MAX = 256
+# enum vr_slice_mode, enum vr_slice_source, VR_SLICE_MAX_SAMPLES
+VR_SLICE_MAX, VR_SLICE_MIN, VR_SLICE_SUM = 0, 1, 2
+VR_SLICE_EMISSION, VR_SLICE_ABSORPTION, VR_SLICE_REFLECTION = 0, 1, 2
+VR_SLICE_MAX_SAMPLES = 4096
 # enum vr_launch_flag: the bits of vr_last_launch_flags, in bit order
 LAUNCH_FLAGS = ("tame", "small_x", "eds_finite", "skip_empty", "re_ok", "lut_ok", "tap_half", "ab_alias", "share",
                 "big", "occ")
@@ -66,6 +70,12 @@ class VrTransfer(ctypes.Structure):
 
 class VrClipPlane(ctypes.Structure):
     _fields_ = [("normal", c_float * 3), ("offset", c_float)]
+
+
+class VrSlice(ctypes.Structure):
+    _fields_ = [("origin", c_float * 3), ("du", c_float * 3), ("dv", c_float * 3), ("dw", c_float * 3),
+                ("resolution", c_uint64 * 2), ("samples", c_int32), ("mode", c_int32), ("source", c_int32),
+                ("reserved", c_int32)]
 
 
 class VrChannel(ctypes.Structure):
@@ -123,6 +133,12 @@ SIGNATURES = [
     ("vr_set_label_gains", c_int, [c_void_p, c_void_p, c_int32]),
     ("vr_get_label_gains", c_int, [c_void_p, c_void_p, POINTER(c_int32)]),
     ("vr_label_gain_host", c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_uint64, c_void_p]),
+    ("vr_render_slice", c_int, [c_void_p, POINTER(VrSlice), c_void_p, c_void_p, c_void_p]),
+    ("vr_render_slice_device", c_int, [c_void_p, POINTER(VrSlice), c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("vr_slice_axis", c_int, [POINTER(c_uint64), c_int32, ctypes.c_double, c_uint64, POINTER(VrSlice)]),
+    ("vr_slice_oblique", c_int, [POINTER(c_uint64), POINTER(c_float), POINTER(ctypes.c_double),
+                                 POINTER(ctypes.c_double), POINTER(ctypes.c_double), ctypes.c_double, c_uint64,
+                                 c_uint64, c_uint64, POINTER(VrSlice)]),
     ("vr_partition_columns", c_int64, [c_int64, POINTER(VrPartition)]),
     ("vr_assemble_partitions", c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int64, c_void_p,
                                        c_void_p]),

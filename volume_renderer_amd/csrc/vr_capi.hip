@@ -32,6 +32,7 @@
 #include "vr_clip.h"
 #include "vr_device.h"
 #include "vr_labels.h"
+#include "vr_slice.h"
 #include "vr_resources.h"
 #include "vr_transfer.h"
 
@@ -96,6 +97,8 @@ hipError_t launch_stats(const float *src, uint64_t n, BufStats *st, hipStream_t 
 hipError_t launch_zpair(const float *src, float *dst, uint32_t n, uint32_t pxy, hipStream_t s);
 hipError_t launch_occupancy(const float *p, uint32_t px, uint32_t py, uint32_t pz, uint8_t *occ, float inv_scale,
                             hipStream_t s);
+// vr_slice.hip: mode = vr_slice_mode
+hipError_t launch_slice(const SliceParams &S, int mode, bool big, hipStream_t s);
 // vr_labels.hip: dst = src under the n gains of `gains` by the dense label bytes; *st += the statistics of dst
 hipError_t launch_label_gain(const float *src, const uint8_t *labels, const float *gains, int32_t n, int32_t nx,
                              int32_t ny, int32_t nz, float *dst, BufStats *st, hipStream_t s);
@@ -383,6 +386,9 @@ struct vr_context {
   int32_t ngains = 0;
   uint64_t gains_version = 0;
   float *d_gains = nullptr;
+  // slices in flight that read d_labels (vr_render_slice_device's label plane): the label bytes are
+  // neither overwritten nor freed before all of them have completed
+  vr_host::Readers labels_readers;
 };
 
 namespace {
@@ -801,6 +807,7 @@ int apply_labels(vr_context *h) {
 }
 
 void free_labels(vr_context *h) {
+  h->labels_readers.wait();
   if (h->d_labels) (void)hipFree(h->d_labels);
   h->d_labels = nullptr;
   h->labels_bytes = 0;
@@ -1847,6 +1854,97 @@ int do_project(vr_context *h, const vr_render_args *a, int32_t mode, const vr_pa
   const vr::ClipSet clip = clip_set(h, P);
   VR_HIP(vr::launch_project(P, mode, d_aux, F.big, probe, stream, &clip));
   VR_HIP(L.finish());
+  return VR_OK;
+}
+
+// The argument checks of vr_render_slice (include/vrhip.h): before the handle, no device needed.
+int check_slice(const vr_slice *s) {
+  if (!s) return fail(VR_ERR_ARGUMENT, "slice: the slice is NULL");
+  for (int i = 0; i < 3; ++i)
+    if (!std::isfinite(s->origin[i]) || !std::isfinite(s->du[i]) || !std::isfinite(s->dv[i]) ||
+        !std::isfinite(s->dw[i]))
+      return fail(VR_ERR_ARGUMENT, "slice: non-finite origin / du / dv / dw");
+  if (s->samples < 1 || s->samples > VR_SLICE_MAX_SAMPLES)
+    return fail(VR_ERR_ARGUMENT, "slice: 1 .. " + std::to_string(VR_SLICE_MAX_SAMPLES) + " samples");
+  if (s->mode != VR_SLICE_MAX && s->mode != VR_SLICE_MIN && s->mode != VR_SLICE_SUM)
+    return fail(VR_ERR_ARGUMENT, "slice: unknown slice mode");
+  if (s->source != VR_SLICE_EMISSION && s->source != VR_SLICE_ABSORPTION && s->source != VR_SLICE_REFLECTION)
+    return fail(VR_ERR_ARGUMENT, "slice: unknown slice source");
+  const uint64_t H = s->resolution[0], W = s->resolution[1];
+  if (H > 0x7FFFFFFFull || W > 0x7FFFFFFFull || H * W >= (1ull << 31))
+    return fail(VR_ERR_ARGUMENT, "slice: image resolution too large (H * W must be below 2^31)");
+  return VR_OK;
+}
+
+// Cache lines (128 B) one row load of a wave touches when neighbouring lanes are `step` apart in q: the
+// lanes' cells lie a = step * dims voxels apart, so they fall into 1 + 63 min(1, |a1| + |a2|) rows of the
+// volume, and a row's share of the lanes spans 63 |a0| / 32 more lines in all; at most one line per lane.
+double slice_lines(const float step[3], const vr::DevTex &t) {
+  const double a0 = std::fabs((double)step[0] * t.nx), a1 = std::fabs((double)step[1] * t.ny),
+               a2 = std::fabs((double)step[2] * t.nz);
+  return std::min(64.0, 1.0 + 63.0 * std::min(1.0, a1 + a2) + 63.0 * a0 / 32.0);
+}
+
+// Which output axis runs along a wave's lanes: the lines a wave touches for its 4 row
+// loads per slab sample plus the lines its stores touch -- 2 per plane along y, the contiguous axis of a
+// column-major plane, 64 per plane along x -- a stored line weighted 4 times a loaded one (measured: a
+// scattered store costs more than a scattered load, profiles/round17).  VR_SLICE_LANES=x|y (test
+// switch) forces either side.
+#define VR_SLICE_STORE_WEIGHT 4.0
+bool slice_lanes_x(const vr_slice *s, const vr::DevTex &t, int planes) {
+  if (const char *ev = test_env("VR_SLICE_LANES")) {
+    if (ev[0] == 'x') return true;
+    if (ev[0] == 'y') return false;
+  }
+  if (!t.p || t.one) return false;  // no gather: the contiguous store decides
+  const double loads = 4.0 * (double)s->samples;
+  return loads * slice_lines(s->du, t) + VR_SLICE_STORE_WEIGHT * 64.0 * planes <
+         loads * slice_lines(s->dv, t) + VR_SLICE_STORE_WEIGHT * 2.0 * planes;
+}
+
+// Slice render (vr_render_slice, vr_slice.hip): the DevTex of the one source texture through the slot
+// indices, as build_frame binds it; no camera, no frame, no lights.  Nothing of the handle, the texture
+// unit or the last launch flags is written.
+int do_slice(vr_context *h, const vr_slice *s, float *d_out, float *d_aux, float *d_lab, hipStream_t stream) {
+  vr::SliceParams S{};
+  S.height = (int32_t)s->resolution[0];
+  S.width = (int32_t)s->resolution[1];
+  const size_t plane = (size_t)S.width * (size_t)S.height;
+  if (plane && !d_out) return fail(VR_ERR_ARGUMENT, "output is NULL");
+  if (!plane) return VR_OK;
+  const int32_t slot = s->source == VR_SLICE_EMISSION ? g_tex.idx_em
+                       : s->source == VR_SLICE_ABSORPTION ? g_tex.idx_ab : g_tex.idx_re;
+  S.tex = dev_tex(g_tex.bind[slot]);  // (getTexture, kernel.cu:127-144)
+  for (int i = 0; i < 3; ++i) {
+    S.origin[i] = s->origin[i];
+    S.du[i] = s->du[i];
+    S.dv[i] = s->dv[i];
+    S.dw[i] = s->dw[i];
+  }
+  S.samples = s->samples;
+  S.out = d_out;
+  S.aux = d_aux;
+  S.lab = d_lab;
+  const bool labels = d_lab && h->d_labels && h->labels_bytes;
+  if (labels) {
+    S.labels = h->d_labels;
+    for (int i = 0; i < 3; ++i) S.ld[i] = (int32_t)h->labels_dims[i];
+  } else if (d_lab) {  // no labels resident: the whole plane is NaN
+    VR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_lab), 0x7fc00000, plane, stream));
+  }
+  S.lanes_x = slice_lanes_x(s, S.tex, 1 + (d_aux ? 1 : 0) + (d_lab ? 1 : 0)) ? 1 : 0;
+  const bool big = is_big(S.tex) || test_flag("VR_FORCE_BIG");
+  LaunchRec L;
+  L.stream = stream;
+  L.device = h->device;
+  bind_reads(L);
+  VR_HIP(vr::launch_slice(S, s->mode, big, stream));
+  VR_HIP(L.finish());
+  if (labels) {
+    vr_host::EventPtr ev;
+    if (vr_host::record_event(stream, ev) == hipSuccess) h->labels_readers.add(ev);
+    else VR_HIP(hipStreamSynchronize(stream));
+  }
   return VR_OK;
 }
 
@@ -3178,6 +3276,137 @@ int vr_render_projection(vr_context *h, const vr_render_args *a, int32_t mode, f
   VR_GUARD_END
 }
 
+int vr_render_slice_device(vr_context *h, const vr_slice *s, float *d_out, float *d_aux, float *d_labels,
+                           void *stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (int rc = check_slice(s)) return rc;
+  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
+  if (!h->children.empty()) return fail(VR_ERR_UNSUPPORTED, "vr_render_slice_device: one-device handles only");
+  VR_GUARD_BEGIN
+  DeviceGuard dg(h->device);
+  vr_host::prune_retired();
+  return do_slice(h, s, d_out, d_aux, d_labels, (hipStream_t)stream);
+  VR_GUARD_END
+}
+
+int vr_render_slice(vr_context *h, const vr_slice *s, float *out, float *out_aux, float *out_labels) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (int rc = check_slice(s)) return rc;
+  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
+  if (!h->children.empty()) return fail(VR_ERR_UNSUPPORTED, "vr_render_slice: one-device handles only");
+  VR_GUARD_BEGIN
+  DeviceGuard dg(h->device);
+  vr_host::prune_retired();
+  // up to three planes in the handle's output buffer: the image, aux, labels
+  const size_t count = (size_t)s->resolution[0] * (size_t)s->resolution[1];
+  const size_t plane = count * sizeof(float);
+  const size_t bytes = 3 * plane;
+  if (plane && !out) return fail(VR_ERR_ARGUMENT, "output is NULL");
+  if (bytes > h->d_out_bytes) {
+    if (h->d_out) VR_HIP(hipFree(h->d_out));
+    h->d_out = nullptr;
+    h->d_out_bytes = 0;
+    VR_HIP(hipMalloc(&h->d_out, bytes));
+    h->d_out_bytes = bytes;
+  }
+  float *d_aux = out_aux ? h->d_out + count : nullptr;
+  float *d_lab = out_labels ? h->d_out + 2 * count : nullptr;
+  const int rc = do_slice(h, s, h->d_out, d_aux, d_lab, nullptr);
+  if (rc) return rc;
+  if (plane) VR_HIP(hipMemcpy(out, h->d_out, plane, hipMemcpyDeviceToHost));
+  if (plane && out_aux) VR_HIP(hipMemcpy(out_aux, d_aux, plane, hipMemcpyDeviceToHost));
+  if (plane && out_labels) VR_HIP(hipMemcpy(out_labels, d_lab, plane, hipMemcpyDeviceToHost));
+  return VR_OK;
+  VR_GUARD_END
+}
+
+static int check_slice_count(uint64_t thickness) {
+  if (thickness < 1 || thickness > VR_SLICE_MAX_SAMPLES)
+    return fail(VR_ERR_ARGUMENT, "slice: thickness must be 1 .. " + std::to_string(VR_SLICE_MAX_SAMPLES));
+  return VR_OK;
+}
+
+int vr_slice_axis(const uint64_t dims[3], int32_t axis, double index, uint64_t thickness, vr_slice *out) {
+  if (!dims || !out) return fail(VR_ERR_ARGUMENT, "slice: dims / out is NULL");
+  if (!dims[0] || !dims[1] || !dims[2]) return fail(VR_ERR_ARGUMENT, "slice: empty volume");
+  if (axis < 0 || axis > 2) return fail(VR_ERR_ARGUMENT, "slice: axis must be 0, 1 or 2");
+  if (!std::isfinite(index)) return fail(VR_ERR_ARGUMENT, "slice: non-finite index");
+  if (int rc = check_slice_count(thickness)) return rc;
+  const int a = axis == 0 ? 1 : 0, b = axis == 2 ? 1 : 2;  // rows along a, columns along b, a < b
+  if (dims[a] > 0x7FFFFFFFull || dims[b] > 0x7FFFFFFFull || dims[a] * dims[b] >= (1ull << 31))
+    return fail(VR_ERR_ARGUMENT, "slice: image resolution too large (H * W must be below 2^31)");
+  for (int j = 0; j < 3; ++j) out->origin[j] = out->du[j] = out->dv[j] = out->dw[j] = 0.f;
+  const double first = index - (double)(thickness - 1) / 2.0;  // voxel index of slab sample 0
+  out->origin[axis] = (float)((first + 0.5) / (double)dims[axis]);
+  out->dw[axis] = (float)(1.0 / (double)dims[axis]);
+  out->origin[a] = (float)(0.5 / (double)dims[a]);
+  out->dv[a] = (float)(1.0 / (double)dims[a]);
+  out->origin[b] = (float)(0.5 / (double)dims[b]);
+  out->du[b] = (float)(1.0 / (double)dims[b]);
+  out->resolution[0] = dims[a];
+  out->resolution[1] = dims[b];
+  out->samples = (int32_t)thickness;
+  return VR_OK;
+}
+
+int vr_slice_oblique(const uint64_t dims[3], const float element_size_um[3], const double point_q[3],
+                     const double normal_um[3], const double up_um[3], double pixel_um, uint64_t H, uint64_t W,
+                     uint64_t thickness, vr_slice *out) {
+  if (!dims || !element_size_um || !point_q || !normal_um || !up_um || !out)
+    return fail(VR_ERR_ARGUMENT, "slice: a pointer is NULL");
+  if (!dims[0] || !dims[1] || !dims[2]) return fail(VR_ERR_ARGUMENT, "slice: empty volume");
+  if (int rc = check_slice_count(thickness)) return rc;
+  if (H > 0x7FFFFFFFull || W > 0x7FFFFFFFull || H * W >= (1ull << 31))
+    return fail(VR_ERR_ARGUMENT, "slice: image resolution too large (H * W must be below 2^31)");
+  if (!std::isfinite(pixel_um) || !(pixel_um > 0.0)) return fail(VR_ERR_ARGUMENT, "slice: pixel size must be positive");
+  double ext[3];  // physical extent of the volume along dims[j]: q_j * ext[j] is a position in um
+  for (int j = 0; j < 3; ++j) {
+    const double es = (double)element_size_um[2 - j];
+    if (!std::isfinite(es) || !(es > 0.0)) return fail(VR_ERR_ARGUMENT, "slice: element size must be positive");
+    if (!std::isfinite(point_q[j]) || !std::isfinite(normal_um[j]) || !std::isfinite(up_um[j]))
+      return fail(VR_ERR_ARGUMENT, "slice: non-finite point / normal / up");
+    ext[j] = (double)dims[j] * es;
+  }
+  auto dot = [](const double *p, const double *q) { return p[0] * q[0] + p[1] * q[1] + p[2] * q[2]; };
+  // scale the directions by their largest component first: no overflow or underflow in the squares
+  double w[3], v[3], u[3];
+  double nmax = 0, umax = 0;
+  for (int j = 0; j < 3; ++j) {
+    nmax = std::max(nmax, std::fabs(normal_um[j]));
+    umax = std::max(umax, std::fabs(up_um[j]));
+  }
+  if (nmax == 0.0) return fail(VR_ERR_ARGUMENT, "slice: zero normal");
+  if (umax == 0.0) return fail(VR_ERR_ARGUMENT, "slice: up is parallel to the normal");
+  for (int j = 0; j < 3; ++j) {
+    w[j] = normal_um[j] / nmax;
+    v[j] = up_um[j] / umax;
+  }
+  const double wl = std::sqrt(dot(w, w));
+  for (int j = 0; j < 3; ++j) w[j] /= wl;
+  const double vl0 = std::sqrt(dot(v, v));
+  for (int j = 0; j < 3; ++j) v[j] /= vl0;
+  const double vw = dot(v, w);
+  for (int j = 0; j < 3; ++j) v[j] -= vw * w[j];
+  const double vl = std::sqrt(dot(v, v));
+  if (!(vl > 1e-9)) return fail(VR_ERR_ARGUMENT, "slice: up is parallel to the normal");
+  for (int j = 0; j < 3; ++j) v[j] /= vl;
+  u[0] = v[1] * w[2] - v[2] * w[1];
+  u[1] = v[2] * w[0] - v[0] * w[2];
+  u[2] = v[0] * w[1] - v[1] * w[0];
+  const double cy = ((double)H - 1.0) / 2.0, cx = ((double)W - 1.0) / 2.0, ck = ((double)thickness - 1.0) / 2.0;
+  for (int j = 0; j < 3; ++j) {
+    const double duq = u[j] * pixel_um / ext[j], dvq = v[j] * pixel_um / ext[j], dwq = w[j] * pixel_um / ext[j];
+    out->du[j] = (float)duq;
+    out->dv[j] = (float)dvq;
+    out->dw[j] = (float)dwq;
+    out->origin[j] = (float)(point_q[j] - cx * duq - cy * dvq - ck * dwq);
+  }
+  out->resolution[0] = H;
+  out->resolution[1] = W;
+  out->samples = (int32_t)thickness;
+  return VR_OK;
+}
+
 int vr_render_isosurface_device(vr_context *h, const vr_render_args *a, float level, const vr_partition *part,
                                 float *d_out, float *d_depth, float *d_normal, unsigned long long *d_steps,
                                 void *stream) {
@@ -3325,6 +3554,7 @@ int vr_sync_labels(vr_context *h, const vr_volume *labels) {
       VR_HIP(vr_host::device_alloc(reinterpret_cast<void **>(&h->d_labels), count));
       h->labels_bytes = count;
     }
+    h->labels_readers.wait();  // slices in flight that read the label bytes
     // (no label pass is in flight: apply_labels waits for its own.)  Device data is read after the work
     // already queued on the null stream, as the upload path reads a device volume.
     const bool dev = labels->location == VR_DEVICE;

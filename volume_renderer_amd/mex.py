@@ -524,6 +524,87 @@ def label_gain_host(src, labels, gains) -> np.ndarray:
     return out.reshape(s.shape, order="F")
 
 
+SLICE_MODES = {"max": _lib.VR_SLICE_MAX, "min": _lib.VR_SLICE_MIN, "sum": _lib.VR_SLICE_SUM}
+SLICE_SOURCES = {"emission": _lib.VR_SLICE_EMISSION, "absorption": _lib.VR_SLICE_ABSORPTION,
+                 "reflection": _lib.VR_SLICE_REFLECTION}
+
+
+def slice_mode(mode) -> int:
+    """The vr_slice_mode code of 'max' / 'min' / 'sum' (or of a code itself)."""
+    if isinstance(mode, str):
+        if mode.lower() not in SLICE_MODES:
+            raise _lib.VrError(1, "slice: unknown slice mode")
+        return SLICE_MODES[mode.lower()]
+    return int(np.asarray(mode).reshape(-1)[0])
+
+
+def slice_source(source) -> int:
+    """The vr_slice_source code of 'emission' / 'absorption' / 'reflection' (or of a code itself)."""
+    if isinstance(source, str):
+        if source.lower() not in SLICE_SOURCES:
+            raise _lib.VrError(1, "slice: unknown slice source")
+        return SLICE_SOURCES[source.lower()]
+    return int(np.asarray(source).reshape(-1)[0])
+
+
+def make_slice(geom, res, n=1, mode="max", source="emission") -> _lib.VrSlice:
+    """A vr_slice from the mex command's arguments: geom 3 x 4 single [origin du dv dw] (columns),
+    res [H W], n slab samples, mode and source as strings or codes.  The library checks the values."""
+    g = np.asarray(geom)
+    if g.dtype != np.float32 or g.shape != (3, 4):
+        raise _lib.VrError(1, "render_slice: geom must be a single 3 x 4 matrix [origin du dv dw]")
+    r = np.asarray(res).reshape(-1)
+    if r.size != 2:
+        raise _lib.VrError(1, "render_slice: res must be [H W]")
+    s = _lib.VrSlice()
+    for j in range(3):
+        s.origin[j], s.du[j], s.dv[j], s.dw[j] = g[j, 0], g[j, 1], g[j, 2], g[j, 3]
+    s.resolution[0], s.resolution[1] = int(r[0]), int(r[1])
+    s.samples = int(np.asarray(n).reshape(-1)[0])
+    s.mode, s.source = slice_mode(mode), slice_source(source)
+    return s
+
+
+def slice_geom(s) -> np.ndarray:
+    """The 3 x 4 single matrix [origin du dv dw] of a vr_slice (the mex command's geom)."""
+    return np.asfortranarray(np.array([list(s.origin), list(s.du), list(s.dv), list(s.dw)], np.float32).T)
+
+
+def slice_axis(dims, axis: int, index: float, thickness: int = 1) -> _lib.VrSlice:
+    """vr_slice_axis: the voxel plane at 0-based `index` along `axis` (0-based) of a volume of `dims`, one
+    pixel per voxel, the lower-numbered remaining dimension along the rows; a slab of `thickness` samples
+    one voxel apart centred on the index.  mode and source are left 0 ('max', 'emission')."""
+    d = (ctypes.c_uint64 * 3)(*(list(int(x) for x in dims) + [1] * (3 - len(dims))))
+    s = _lib.VrSlice()
+    check(lib().vr_slice_axis(d, int(axis), float(index), int(thickness), ctypes.byref(s)))
+    return s
+
+
+def slice_oblique(dims, element_size_um, point_q, normal_um, up_um, pixel_um: float, H: int, W: int,
+                  thickness: int = 1) -> _lib.VrSlice:
+    """vr_slice_oblique: the H x W plane through point_q (normalized volume coordinate, the image centre)
+    with physical normal normal_um and rows along up_um projected into the plane, pixels and slab samples
+    pixel_um apart; element_size_um in MATLAB order, the directions with component j along dims[j]."""
+    d = (ctypes.c_uint64 * 3)(*(list(int(x) for x in dims) + [1] * (3 - len(dims))))
+    es = (ctypes.c_float * 3)(*[float(x) for x in _f32(element_size_um, 3, "ElementSizeUm")])
+    vec = [(ctypes.c_double * 3)(*[float(x) for x in np.asarray(v, np.float64).reshape(-1)[:3]])
+           for v in (point_q, normal_um, up_um)]
+    s = _lib.VrSlice()
+    check(lib().vr_slice_oblique(d, es, vec[0], vec[1], vec[2], float(pixel_um), int(H), int(W), int(thickness),
+                                 ctypes.byref(s)))
+    return s
+
+
+def render_slice_device(handle, s, d_out: int, d_aux: int = 0, d_labels: int = 0, stream: int = 0) -> None:
+    """A slice into device memory (vr_render_slice_device), asynchronous on `stream`: s from make_slice /
+    slice_axis / slice_oblique; planes [H, W] column-major; d_aux = 0 / d_labels = 0: no such plane."""
+    check(lib().vr_render_slice_device(_handle(handle), ctypes.byref(s),
+                                       ctypes.c_void_p(int(d_out)) if d_out else None,
+                                       ctypes.c_void_p(int(d_aux)) if d_aux else None,
+                                       ctypes.c_void_p(int(d_labels)) if d_labels else None,
+                                       ctypes.c_void_p(int(stream)) if stream else None))
+
+
 def set_option(name: str, value: int) -> None:
     """vr_set_option: a process-wide library option (include/vrhip.h)."""
     check(lib().vr_set_option(name.encode(), int(value)))
@@ -670,7 +751,7 @@ def _group_devices():
 def volumeRender(cmd, *args):
     """The `volumeRender` mex: commands 'new', 'delete', 'mem_info', 'sync_volumes', 'render' (and
     'render_stereo', 'render_channels', 'render_projection', 'render_isosurface', 'render_transfer',
-    'set_clip', 'sync_labels', 'set_label_gains', which the reference does not have)."""
+    'render_slice', 'set_clip', 'sync_labels', 'set_label_gains', which the reference does not have)."""
     nrhs = 1 + len(args)
     if not isinstance(cmd, str) or len(cmd) >= 64:
         raise _lib.VrError(1, "First input should be a command string less than 64 characters long.")
@@ -778,6 +859,19 @@ def volumeRender(cmd, *args):
                                      aux.ctypes.data_as(ctypes.c_void_p) if aux.size else None))
         del keep
         return out, aux
+    if cmd == "render_slice":  # ('render_slice', h, geom 3 x 4 single, res [H W], n, mode, source)
+        if nrhs < 7:
+            raise _lib.VrError(1, "insufficient parameter!")
+        if nrhs > 7:
+            raise _lib.VrError(1, "render_slice: too many input arguments")
+        s = make_slice(*args[1:6])
+        H, W = int(s.resolution[0]), int(s.resolution[1])
+        if H >= 2 ** 31 or W >= 2 ** 31 or H * W >= 2 ** 31:
+            raise _lib.VrError(1, "slice: image resolution too large (H * W must be below 2^31)")
+        img, aux, lab = (np.zeros((H, W), dtype=np.float32, order="F") for _ in range(3))
+        check(L.vr_render_slice(h, ctypes.byref(s), *(p.ctypes.data_as(ctypes.c_void_p) if p.size else None
+                                                      for p in (img, aux, lab))))
+        return img, aux, lab
     if cmd == "render_isosurface":  # ('render_isosurface', h, <the nine render arguments>, level)
         if nrhs < 12:
             raise _lib.VrError(1, "insufficient parameter!")

@@ -265,6 +265,55 @@ class VolumeRender:
         return volumeRender("render_projection", self.objectHandle, *self._render_argv(camera_x_offset, resolution),
                             mode)
 
+    def renderSlice(self, axis=None, index=None, point=None, normal=None, up=None, pixel_size_um=None,
+                    resolution=None, thickness=1, mode="max", source="emission", aux=False, labels=False):
+        """A section through a resident volume (vr_render_slice): what the renderer samples -- a typed
+        upload widened, label gains applied -- on a plane, [H, W] single.
+        Axis slice: `axis` (1-based dimension of Data, as MATLAB counts) and `index` (1-based voxel
+        plane, fractions allowed): one pixel per voxel, the lower-numbered remaining dimension along the
+        rows.  Oblique slice: `point` (normalized volume coordinate q of the image centre, dimension
+        order of Data), `normal` and `up` (physical directions, component j along dimension j),
+        `pixel_size_um` (default: the smallest ElementSizeUm) and `resolution` [H W] (default
+        ImageResolution flipped); the plane is orthonormal in physical space, rows along `up`.
+        `thickness` slab samples (one voxel resp. one pixel size apart, centred) are reduced by `mode`
+        'max' | 'min' | 'mean' | 'sum'; `source` 'emission' | 'absorption' | 'reflection'.  Pixels whose
+        every sample lies outside the volume are NaN.  aux=True also returns the aux plane (the sample
+        index of the extremum, resp. the count of inside samples), labels=True the label plane (the
+        label at the slab's centre, NaN outside or without VolumeLabels).  ClipPlanes are ignored: the
+        slice is itself the cut."""
+        from . import mex
+        m = mode.lower() if isinstance(mode, str) else mode
+        mean = m == "mean"
+        code = mex.slice_mode("sum" if mean else m)
+        src = mex.slice_source(source)
+        vol = (self.VolumeEmission, self.VolumeAbsorption, self.VolumeReflection)[src]
+        dims = vol.dims if hasattr(vol, "dims") else mex._matlab_dims(
+            vol.RawData if getattr(getattr(vol, "RawData", None), "size", 0) else vol.Data)
+        if axis is not None:
+            if index is None or point is not None or normal is not None:
+                raise ValueError("renderSlice: give 'axis' and 'index', or 'point' and 'normal'")
+            s = mex.slice_axis(dims, int(axis) - 1, float(index) - 1.0, int(thickness))
+        else:
+            if point is None or normal is None:
+                raise ValueError("renderSlice: give 'axis' and 'index', or 'point' and 'normal'")
+            es = np.asarray(self.ElementSizeUm, np.float32)
+            if up is None:  # any direction that is not the normal's: the dimension the normal leans on least
+                up = np.zeros(3)
+                up[int(np.argmin(np.abs(np.asarray(normal, np.float64).reshape(-1)[:3])))] = 1.0
+            res = np.flip(self.ImageResolution) if resolution is None else np.asarray(resolution).reshape(-1)
+            px = float(es.min()) if pixel_size_um is None else float(pixel_size_um)
+            s = mex.slice_oblique(dims, es, point, normal, up, px, int(res[0]), int(res[1]), int(thickness))
+        self._validate_volumes()
+        self._apply_labels()
+        self.syncVolumes()
+        img, plane, lab = volumeRender("render_slice", self.objectHandle, mex.slice_geom(s),
+                                       np.uint64([s.resolution[0], s.resolution[1]]), np.int32(s.samples), code, src)
+        if mean:
+            with np.errstate(all="ignore"):
+                img = (img / plane).astype(np.float32)
+        out = (img,) + ((plane,) if aux else ()) + ((lab,) if labels else ())
+        return out if len(out) > 1 else img
+
     def renderIsosurface(self, level, aux=False):
         """The first-hit isosurface VolumeEmission == level through the current camera
         (vr_render_isosurface): the opaque surface lit by LightSources / VolumeIllumination plus
