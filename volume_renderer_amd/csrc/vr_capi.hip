@@ -1152,6 +1152,28 @@ void upload_lights(vr_context *h, const vr_render_args *a) {
   sync_volume_if_changed(h, T_LIGHT, T_LIGHT);
 }
 
+// The lights / LUT arguments of a lit render: the argument checks, the memory check of the LUT beside
+// the handle's volumes, then upload_lights.  required (optional): that memory, for the caller's own
+// check of what it allocates on top.
+int check_lights(const vr_render_args *a) {
+  if (a->num_lights > 0 && !a->lights) return fail(VR_ERR_ARGUMENT, "lights is NULL");
+  if (a->num_lights >= 0)
+    if (int rc = check_dtype(a->illumination, true, "illumination volume")) return rc;
+  return VR_OK;
+}
+int check_and_upload_lights(vr_context *h, const vr_render_args *a, uint64_t *required = nullptr) {
+  if (int rc = check_lights(a)) return rc;
+  uint64_t need = required_memory(h);
+  if (a->num_lights >= 0 && a->illumination) {
+    need += a->illumination->dims[0] * a->illumination->dims[1] * a->illumination->dims[2] * 4 +
+            (uint64_t)a->num_lights * sizeof(vr::DevLight);
+    if (int rc = check_free_device_memory(need)) return rc;
+  }
+  upload_lights(h, a);
+  if (required) *required = need;
+  return VR_OK;
+}
+
 // What a launch reads (vr_resources.h): every bound texture buffer (and the interleaved lookup
 // gradient) is marked with the launch's completion event by finish(); the frame's light list is
 // staged on the launch stream.
@@ -1171,10 +1193,22 @@ void bind_reads(LaunchRec &L) {
       L.reads.push_back(kv.second.buf);
     }
 }
+LaunchRec launch_rec(const vr_context *h, hipStream_t stream) {  // a launch of h's device that reads the bound textures
+  LaunchRec L;
+  L.stream = stream;
+  L.device = h->device;
+  bind_reads(L);
+  return L;
+}
 void stage_frame(LaunchRec &L, vr::RenderParams &P, const std::vector<vr::DevLight> &lights) {
   const void *d = nullptr;
   VR_HIP(L.stage(lights.data(), lights.size() * sizeof(vr::DevLight), &d));
   P.lights = static_cast<const vr::DevLight *>(d);
+}
+// `count` floats of an output plane set to one bit pattern (a degenerate frame's zeros and NaNs)
+constexpr uint32_t VR_QNAN_BITS = 0x7fc00000u;  // the quiet NaN the kernels write for "no value"
+void fill_plane(float *d, uint32_t bits, size_t count, hipStream_t stream) {
+  if (d && count) VR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d), (int)bits, count, stream));
 }
 
 int64_t part_columns(int64_t w, int32_t bc, int32_t part, int32_t np) {
@@ -1191,6 +1225,19 @@ int validate_partition(const vr_partition *p) {
   if (p->num_parts < 1 || p->part < 0 || p->part >= p->num_parts || p->block_cols < 1)
     return fail(VR_ERR_ARGUMENT, "invalid partition");
   return VR_OK;
+}
+
+// The partition fields of a launch's RenderParams (part null: the whole image), its output and counters;
+// row-major tiles.  plane_cols: the widest part's columns, the stride of every part's planes.
+void set_partition(vr::RenderParams &P, const vr_partition *part, float *d_out, unsigned long long *d_steps) {
+  P.block_cols = part ? part->block_cols : std::max<int32_t>(P.width, 1);
+  P.part = part ? part->part : 0;
+  P.num_parts = part ? part->num_parts : 1;
+  P.part_cols = (int32_t)part_columns(P.width, P.block_cols, P.part, P.num_parts);
+  P.plane_cols = (int32_t)part_columns(P.width, P.block_cols, 0, P.num_parts);
+  P.out = d_out;
+  P.steps = d_steps;
+  P.tile_mode = 0;
 }
 
 
@@ -1572,33 +1619,18 @@ int do_render(vr_context *h, const vr_render_args *a, const vr_partition *part, 
               unsigned long long *d_steps, hipStream_t stream, Frame &F, float *d_out2 = nullptr,
               const float *eye2 = nullptr, int *fusable = nullptr) {
   if (fusable) *fusable = 0;
-  if (a->num_lights > 0 && !a->lights) return fail(VR_ERR_ARGUMENT, "lights is NULL");
-  if (a->num_lights >= 0)
-    if (int rc = check_dtype(a->illumination, true, "illumination volume")) return rc;
-  uint64_t required = required_memory(h);
-  if (a->num_lights >= 0 && a->illumination) {
-    required += a->illumination->dims[0] * a->illumination->dims[1] * a->illumination->dims[2] * 4 +
-                (uint64_t)a->num_lights * sizeof(vr::DevLight);
-    int rc = check_free_device_memory(required);
-    if (rc) return rc;
-  }
-  upload_lights(h, a);
+  uint64_t required = 0;
+  int rc = check_and_upload_lights(h, a, &required);
+  if (rc) return rc;
   required += a->resolution[0] * a->resolution[1] * sizeof(float) * 3;
-  int rc = check_free_device_memory(required);
+  rc = check_free_device_memory(required);
   if (rc) return rc;
   rc = build_frame(h, a, F);
   if (rc) return rc;
   rc = validate_partition(part);
   if (rc) return rc;
   vr::RenderParams &P = F.P;
-  P.block_cols = part ? part->block_cols : std::max<int32_t>(P.width, 1);
-  P.part = part ? part->part : 0;
-  P.num_parts = part ? part->num_parts : 1;
-  P.part_cols = (int32_t)part_columns(P.width, P.block_cols, P.part, P.num_parts);
-  P.plane_cols = (int32_t)part_columns(P.width, P.block_cols, 0, P.num_parts);
-  P.out = d_out;
-  P.steps = d_steps;
-  P.tile_mode = 0;
+  set_partition(P, part, d_out, d_steps);
   P.lookup = F.mode == 2 ? 1 : 0;
   set_tau_and_slot(P, a, (double)h->vol[T_EM].dims[0]);  // depth lanes and wave slot size
   // shading arithmetic: hardware rsq / exp2 by default; VR_EXACT_SHADE=1 selects
@@ -1671,10 +1703,7 @@ int do_render(vr_context *h, const vr_render_args *a, const vr_partition *part, 
     *fusable = 1;
     return VR_OK;
   }
-  LaunchRec L;
-  L.stream = stream;
-  L.device = h->device;
-  bind_reads(L);
+  LaunchRec L = launch_rec(h, stream);
   stage_frame(L, P, g_tex.lights);
   if (march) {
     // the counter variant: K = 1 (VR_COUNT_PROD=1 with a VR_COUNT_K=1 build: the production K's chunk
@@ -1816,7 +1845,7 @@ int do_render(vr_context *h, const vr_render_args *a, const vr_partition *part, 
 }
 
 // Projection render (vr_render_projection, vr_project.hip): the frame geometry, the probe margin and
-// the occupancy pointers of build_frame and the partition fields of do_render; no lights are
+// the occupancy pointers of build_frame and the partition fields of set_partition; no lights are
 // uploaded or staged, and nothing of the texture unit, the slot indices or the march's schedules is
 // written -- a render before and after a projection gives the same bits.
 int do_project(vr_context *h, const vr_render_args *a, int32_t mode, const vr_partition *part, float *d_out,
@@ -1827,30 +1856,18 @@ int do_project(vr_context *h, const vr_render_args *a, int32_t mode, const vr_pa
   rc = validate_partition(part);
   if (rc) return rc;
   vr::RenderParams &P = F.P;
-  P.block_cols = part ? part->block_cols : std::max<int32_t>(P.width, 1);
-  P.part = part ? part->part : 0;
-  P.num_parts = part ? part->num_parts : 1;
-  P.part_cols = (int32_t)part_columns(P.width, P.block_cols, P.part, P.num_parts);
-  P.plane_cols = (int32_t)part_columns(P.width, P.block_cols, 0, P.num_parts);
-  P.out = d_out;
-  P.steps = d_steps;
-  P.tile_mode = 0;
+  set_partition(P, part, d_out, d_steps);
   P.views = 1;
   const size_t plane = (size_t)P.plane_cols * (size_t)P.height;
   if (plane && !d_out) return fail(VR_ERR_ARGUMENT, "output is NULL");
   if (F.degenerate) {  // no synced emission volume: render's zeros, and every ray a miss
-    if (plane) VR_HIP(hipMemsetAsync(d_out, 0, plane * 3 * sizeof(float), stream));
-    if (plane && d_aux)
-      VR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_aux), mode == VR_PROJ_MIP ? 0x7fc00000 : 0, plane,
-                               stream));
+    fill_plane(d_out, 0u, plane * 3, stream);
+    fill_plane(d_aux, mode == VR_PROJ_MIP ? VR_QNAN_BITS : 0u, plane, stream);
     return VR_OK;
   }
   // VR_PROJ_NO_PROBE=1 (test switch): every sample fetched, no empty-space leap
   const bool probe = P.occ != nullptr && !test_flag("VR_PROJ_NO_PROBE");
-  LaunchRec L;
-  L.stream = stream;
-  L.device = h->device;
-  bind_reads(L);
+  LaunchRec L = launch_rec(h, stream);
   const vr::ClipSet clip = clip_set(h, P);
   VR_HIP(vr::launch_project(P, mode, d_aux, F.big, probe, stream, &clip));
   VR_HIP(L.finish());
@@ -1929,15 +1946,12 @@ int do_slice(vr_context *h, const vr_slice *s, float *d_out, float *d_aux, float
   if (labels) {
     S.labels = h->d_labels;
     for (int i = 0; i < 3; ++i) S.ld[i] = (int32_t)h->labels_dims[i];
-  } else if (d_lab) {  // no labels resident: the whole plane is NaN
-    VR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_lab), 0x7fc00000, plane, stream));
+  } else {  // no labels resident: the whole plane is NaN
+    fill_plane(d_lab, VR_QNAN_BITS, plane, stream);
   }
   S.lanes_x = slice_lanes_x(s, S.tex, 1 + (d_aux ? 1 : 0) + (d_lab ? 1 : 0)) ? 1 : 0;
   const bool big = is_big(S.tex) || test_flag("VR_FORCE_BIG");
-  LaunchRec L;
-  L.stream = stream;
-  L.device = h->device;
-  bind_reads(L);
+  LaunchRec L = launch_rec(h, stream);
   VR_HIP(vr::launch_slice(S, s->mode, big, stream));
   VR_HIP(L.finish());
   if (labels) {
@@ -1949,55 +1963,35 @@ int do_slice(vr_context *h, const vr_slice *s, float *d_out, float *d_aux, float
 }
 
 // Isosurface render (vr_render_isosurface, vr_isosurface.hip): the lights and the LUT uploaded and
-// checked as do_render does, the frame geometry, the probe margin and the occupancy pointers of
-// build_frame, the partition fields of do_project.  The gradient method is the handle's whether or
+// checked (check_and_upload_lights), the frame geometry, the probe margin and the occupancy pointers of
+// build_frame, the partition fields of set_partition.  The gradient method is the handle's whether or
 // not there are lights (the normal plane needs it).  Only the handle's light and LUT state is
 // written, as by a render: nothing of the texture unit, the slot indices or the march's schedules.
 int do_isosurface(vr_context *h, const vr_render_args *a, float level, const vr_partition *part, float *d_out,
                   float *d_depth, float *d_normal, unsigned long long *d_steps, hipStream_t stream) {
-  if (a->num_lights > 0 && !a->lights) return fail(VR_ERR_ARGUMENT, "lights is NULL");
-  if (a->num_lights >= 0)
-    if (int rc = check_dtype(a->illumination, true, "illumination volume")) return rc;
-  if (a->num_lights >= 0 && a->illumination) {
-    const uint64_t required = required_memory(h) +
-                              a->illumination->dims[0] * a->illumination->dims[1] * a->illumination->dims[2] * 4 +
-                              (uint64_t)a->num_lights * sizeof(vr::DevLight);
-    if (int rc = check_free_device_memory(required)) return rc;
-  }
-  upload_lights(h, a);
+  int rc = check_and_upload_lights(h, a);
+  if (rc) return rc;
   Frame F;
-  int rc = build_frame(h, a, F);
+  rc = build_frame(h, a, F);
   if (rc) return rc;
   rc = validate_partition(part);
   if (rc) return rc;
   vr::RenderParams &P = F.P;
-  P.block_cols = part ? part->block_cols : std::max<int32_t>(P.width, 1);
-  P.part = part ? part->part : 0;
-  P.num_parts = part ? part->num_parts : 1;
-  P.part_cols = (int32_t)part_columns(P.width, P.block_cols, P.part, P.num_parts);
-  P.plane_cols = (int32_t)part_columns(P.width, P.block_cols, 0, P.num_parts);
-  P.out = d_out;
-  P.steps = d_steps;
-  P.tile_mode = 0;
+  set_partition(P, part, d_out, d_steps);
   P.views = 1;
   P.fast_shade = 0;
   if (P.lut.p == nullptr) P.num_lights = 0;  // no LUT: no illumination term
   const size_t plane = (size_t)P.plane_cols * (size_t)P.height;
   if (plane && !d_out) return fail(VR_ERR_ARGUMENT, "output is NULL");
   if (F.degenerate) {  // no synced emission volume: no surface anywhere
-    if (plane) VR_HIP(hipMemsetAsync(d_out, 0, plane * 3 * sizeof(float), stream));
-    if (plane && d_depth)
-      VR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_depth), 0x7fc00000, plane, stream));
-    if (plane && d_normal)
-      VR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_normal), 0x7fc00000, plane * 3, stream));
+    fill_plane(d_out, 0u, plane * 3, stream);
+    fill_plane(d_depth, VR_QNAN_BITS, plane, stream);
+    fill_plane(d_normal, VR_QNAN_BITS, plane * 3, stream);
     return VR_OK;
   }
   // VR_ISO_NO_PROBE=1 (test switch): every sample fetched, no empty-space leap
   const bool probe = P.occ != nullptr && level > 0.f && !test_flag("VR_ISO_NO_PROBE");
-  LaunchRec L;
-  L.stream = stream;
-  L.device = h->device;
-  bind_reads(L);
+  LaunchRec L = launch_rec(h, stream);
   stage_frame(L, P, g_tex.lights);
   const vr::ClipSet clip = clip_set(h, P);
   VR_HIP(vr::launch_isosurface(P, g_tex.grad_method == G_LOOKUP ? 2 : 1, level, d_depth, d_normal, F.big, probe,
@@ -2063,45 +2057,30 @@ std::map<int, TableRing> &table_rings() {
 }
 
 // Transfer-function render (vr_render_transfer, vr_transfer.hip): the lights and the LUT uploaded and
-// checked as do_isosurface does, the frame of build_frame, the partition fields of do_project.  The
+// checked (check_and_upload_lights), the frame of build_frame, the partition fields of set_partition.  The
 // tables travel as segment records {T[i], T[i+1] - T[i]} in the launch's staged constants, in front of
 // the light list: one copy ordered on the launch's stream, through ConstRing up to 4 KiB and through
 // TableRing above (only a light list that pushes the payload past 48 KiB takes LaunchRec's dedicated
 // allocation, as a render's would).  Only the handle's light and LUT state is written, as by a render.
 int do_transfer(vr_context *h, const vr_render_args *a, const vr_transfer *tf, const vr_partition *part, float *d_out,
                 float *d_alpha, unsigned long long *d_steps, hipStream_t stream) {
-  if (a->num_lights > 0 && !a->lights) return fail(VR_ERR_ARGUMENT, "lights is NULL");
-  if (a->num_lights >= 0)
-    if (int rc = check_dtype(a->illumination, true, "illumination volume")) return rc;
-  if (a->num_lights >= 0 && a->illumination) {
-    const uint64_t required = required_memory(h) +
-                              a->illumination->dims[0] * a->illumination->dims[1] * a->illumination->dims[2] * 4 +
-                              (uint64_t)a->num_lights * sizeof(vr::DevLight);
-    if (int rc = check_free_device_memory(required)) return rc;
-  }
-  upload_lights(h, a);
+  int rc = check_and_upload_lights(h, a);
+  if (rc) return rc;
   Frame F;
-  int rc = build_frame(h, a, F);
+  rc = build_frame(h, a, F);
   if (rc) return rc;
   rc = validate_partition(part);
   if (rc) return rc;
   vr::RenderParams &P = F.P;
-  P.block_cols = part ? part->block_cols : std::max<int32_t>(P.width, 1);
-  P.part = part ? part->part : 0;
-  P.num_parts = part ? part->num_parts : 1;
-  P.part_cols = (int32_t)part_columns(P.width, P.block_cols, P.part, P.num_parts);
-  P.plane_cols = (int32_t)part_columns(P.width, P.block_cols, 0, P.num_parts);
-  P.out = d_out;
-  P.steps = d_steps;
-  P.tile_mode = 0;
+  set_partition(P, part, d_out, d_steps);
   P.views = 1;
   P.fast_shade = 0;
   if (P.lut.p == nullptr) P.num_lights = 0;  // no LUT: no illumination term
   const size_t plane = (size_t)P.plane_cols * (size_t)P.height;
   if (plane && !d_out) return fail(VR_ERR_ARGUMENT, "output is NULL");
   if (F.degenerate) {  // no synced emission volume: zeros everywhere
-    if (plane) VR_HIP(hipMemsetAsync(d_out, 0, plane * 3 * sizeof(float), stream));
-    if (plane && d_alpha) VR_HIP(hipMemsetAsync(d_alpha, 0, plane * sizeof(float), stream));
+    fill_plane(d_out, 0u, plane * 3, stream);
+    fill_plane(d_alpha, 0u, plane, stream);
     return VR_OK;
   }
   const int grad = P.num_lights == 0 ? 0 : (g_tex.grad_method == G_LOOKUP ? 2 : 1);
@@ -2139,10 +2118,7 @@ int do_transfer(vr_context *h, const vr_render_args *a, const vr_transfer *tf, c
     const float A = na ? transfer_lookup(tf->alphamap, na, tf->alim, z) : z;
     probe = probe && (P.fa * A) * P.tstep == 0.f;
   }
-  LaunchRec L;
-  L.stream = stream;
-  L.device = h->device;
-  bind_reads(L);
+  LaunchRec L = launch_rec(h, stream);
   const void *d_blob = nullptr;
   const size_t blob_bytes = blob.size() * sizeof(float);
   TableRing *ring = nullptr;
@@ -2187,11 +2163,10 @@ int do_render_slab(vr_context *h, const vr_render_args *a, const vr_slab *sl, co
   if (!sl || !d_out) return fail(VR_ERR_ARGUMENT, "slab / output is NULL");
   if (sl->depth == 0 || sl->z_first >= sl->depth || (sl->direction < -1 || sl->direction > 1))
     return fail(VR_ERR_ARGUMENT, "invalid slab");
-  if (a->num_lights > 0 && !a->lights) return fail(VR_ERR_ARGUMENT, "lights is NULL");
-  if (a->num_lights >= 0)
-    if (int rc = check_dtype(a->illumination, true, "illumination volume")) return rc;
+  int rc = check_lights(a);  // (the argument checks alone: a slab render makes no memory check)
+  if (rc) return rc;
   upload_lights(h, a);
-  int rc = build_frame(h, a, F, sl->depth);
+  rc = build_frame(h, a, F, sl->depth);
   if (rc) return rc;
   vr::RenderParams &P = F.P;
   if (F.degenerate || !P.em.p || P.em.one) return fail(VR_ERR_UNSUPPORTED, "slab render needs a synced emission volume");
@@ -2231,16 +2206,11 @@ int do_render_slab(vr_context *h, const vr_render_args *a, const vr_slab *sl, co
   P.slab_in = d_in;
   rc = validate_partition(part);
   if (rc) return rc;
-  P.block_cols = part ? part->block_cols : std::max<int32_t>(P.width, 1);
-  P.part = part ? part->part : 0;
-  P.num_parts = part ? part->num_parts : 1;
-  P.part_cols = (int32_t)part_columns(P.width, P.block_cols, P.part, P.num_parts);
+  set_partition(P, part, d_out, nullptr);
   P.plane_cols = P.part_cols;  // the state of a part is dense: VR_SLAB_PLANES [part_cols][H] planes
   if ((uint64_t)P.part_cols * (uint64_t)P.height >= (1ull << 32))
     return fail(VR_ERR_UNSUPPORTED, "slab render: more than 2^32 rays in one part");
-  P.out = d_out;
   P.fast_shade = env_flag("VR_EXACT_SHADE") ? 0 : 1;
-  P.steps = nullptr;
   // depth lanes (and slot) as for the one-volume march of the whole frame: the tiles of a sweep run
   // back to back and overlap on the sweep's streams, so one tile's launch tail is not the frame's
   // (4 tiles on one MI355X: 1.25x the plain render at the frame's K = 2, 1.36x at a tile's K = 4)
@@ -2258,10 +2228,7 @@ int do_render_slab(vr_context *h, const vr_render_args *a, const vr_slab *sl, co
       {vr::exact::launch_march_slab_k1, vr::exact::launch_march_slab_k2,
        VR_EXACT_K4(vr::exact::launch_march_slab_k4, vr::exact::launch_march_slab_k2)},
       {vr::fast::launch_march_slab_k1, vr::fast::launch_march_slab_k2, vr::fast::launch_march_slab_k4}};
-  LaunchRec L;
-  L.stream = stream;
-  L.device = h->device;
-  bind_reads(L);
+  LaunchRec L = launch_rec(h, stream);
   stage_frame(L, P, g_tex.lights);
   if (K > 1 && want_schedule(P) && short_launch(P)) {  // a tile of a sweep: longest-first schedule
     char extra[120];
@@ -2575,6 +2542,27 @@ void delete_children(vr_context *h) {
   catch (const std::bad_alloc &) {                                                               \
     return fail(VR_ERR_DEVICE, "host out of memory");                                            \
   }
+// The preamble of a single-handle entry, after its lock and its own argument checks (which win over
+// these): the handle, the arguments `a`, one device; then the guard opens on the handle's device and
+// buffers whose last launch has completed are released.  Closed by VR_GUARD_END.
+#define VR_ENTRY_BEGIN(h, a)                                                                        \
+  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");                                   \
+  if (!(a)) return fail(VR_ERR_ARGUMENT, "insufficient parameter!");                                \
+  if (!(h)->children.empty())                                                                       \
+    return fail(VR_ERR_UNSUPPORTED, std::string(__func__) + ": one-device handles only");           \
+  VR_GUARD_BEGIN                                                                                    \
+  DeviceGuard dg((h)->device);                                                                      \
+  vr_host::prune_retired();
+
+// The handle's output buffer (the images and aux planes of the host-pointer renders), at least `bytes`.
+void ensure_out(vr_context *h, size_t bytes) {
+  if (bytes <= h->d_out_bytes) return;
+  if (h->d_out) VR_HIP(hipFree(h->d_out));
+  h->d_out = nullptr;
+  h->d_out_bytes = 0;
+  VR_HIP(hipMalloc(&h->d_out, bytes));
+  h->d_out_bytes = bytes;
+}
 
 double mb(uint64_t b) { return (double)b / (1024.0 * 1024.0); }
 
@@ -3140,13 +3128,7 @@ int vr_render(vr_context *h, const vr_render_args *a, float *out) {
   vr_host::prune_retired();  // buffers whose last launch has completed
   const size_t bytes = (size_t)a->resolution[0] * (size_t)a->resolution[1] * 3 * sizeof(float);
   if (bytes && !out) return fail(VR_ERR_ARGUMENT, "output is NULL");
-  if (bytes > h->d_out_bytes) {
-    if (h->d_out) VR_HIP(hipFree(h->d_out));
-    h->d_out = nullptr;
-    h->d_out_bytes = 0;
-    VR_HIP(hipMalloc(&h->d_out, bytes));
-    h->d_out_bytes = bytes;
-  }
+  ensure_out(h, bytes);
   if (!h->children.empty() && h->nclip) return clip_unsupported("vr_render on a multi-device group handle");
   Frame F;
   int rc = h->children.empty() ? do_render(h, a, nullptr, h->d_out, nullptr, nullptr, F)
@@ -3167,13 +3149,7 @@ int vr_render_stereo(vr_context *h, const vr_render_args *a, float base, float *
   const size_t bytes = (size_t)a->resolution[0] * (size_t)a->resolution[1] * 3 * sizeof(float);
   if (bytes && (!out_left || !out_right)) return fail(VR_ERR_ARGUMENT, "output is NULL");
   if (!h->children.empty() && h->nclip) return clip_unsupported("vr_render_stereo on a multi-device group handle");
-  if (2 * bytes > h->d_out_bytes) {
-    if (h->d_out) VR_HIP(hipFree(h->d_out));
-    h->d_out = nullptr;
-    h->d_out_bytes = 0;
-    VR_HIP(hipMalloc(&h->d_out, 2 * bytes));
-    h->d_out_bytes = 2 * bytes;
-  }
+  ensure_out(h, 2 * bytes);
   // left eye: camera x offset -base (the frame's own eye); right eye: +base, formed as build_frame
   // forms it (fma(-dist, Z, xoff * X), render.cpp:211-221 column order)
   vr_render_args al = *a;
@@ -3199,12 +3175,7 @@ int vr_render_stereo(vr_context *h, const vr_render_args *a, float base, float *
 int vr_render_stereo_device(vr_context *h, const vr_render_args *a, float base, float *d_left, float *d_right,
                             unsigned long long *d_steps, void *stream) {
   std::lock_guard<std::mutex> lk(g_mu);
-  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
-  if (!a) return fail(VR_ERR_ARGUMENT, "insufficient parameter!");
-  if (!h->children.empty()) return fail(VR_ERR_UNSUPPORTED, "vr_render_stereo_device: one-device handles only");
-  VR_GUARD_BEGIN
-  DeviceGuard dg(h->device);
-  vr_host::prune_retired();
+  VR_ENTRY_BEGIN(h, a)
   if ((size_t)a->resolution[0] * (size_t)a->resolution[1] && (!d_left || !d_right))
     return fail(VR_ERR_ARGUMENT, "output is NULL");
   vr_render_args al = *a;  // as vr_render_stereo: left = -base (the frame's eye), right = +base
@@ -3237,12 +3208,7 @@ int vr_render_projection_device(vr_context *h, const vr_render_args *a, int32_t 
                                 float *d_out, float *d_aux, unsigned long long *d_steps, void *stream) {
   std::lock_guard<std::mutex> lk(g_mu);
   if (mode != VR_PROJ_MIP && mode != VR_PROJ_SUM) return fail(VR_ERR_ARGUMENT, "unknown projection mode");
-  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
-  if (!a) return fail(VR_ERR_ARGUMENT, "insufficient parameter!");
-  if (!h->children.empty()) return fail(VR_ERR_UNSUPPORTED, "vr_render_projection_device: one-device handles only");
-  VR_GUARD_BEGIN
-  DeviceGuard dg(h->device);
-  vr_host::prune_retired();
+  VR_ENTRY_BEGIN(h, a)
   return do_project(h, a, mode, part, d_out, d_aux, d_steps, (hipStream_t)stream);
   VR_GUARD_END
 }
@@ -3250,23 +3216,12 @@ int vr_render_projection_device(vr_context *h, const vr_render_args *a, int32_t 
 int vr_render_projection(vr_context *h, const vr_render_args *a, int32_t mode, float *out, float *out_aux) {
   std::lock_guard<std::mutex> lk(g_mu);
   if (mode != VR_PROJ_MIP && mode != VR_PROJ_SUM) return fail(VR_ERR_ARGUMENT, "unknown projection mode");
-  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
-  if (!a) return fail(VR_ERR_ARGUMENT, "insufficient parameter!");
-  if (!h->children.empty()) return fail(VR_ERR_UNSUPPORTED, "vr_render_projection: one-device handles only");
-  VR_GUARD_BEGIN
-  DeviceGuard dg(h->device);
-  vr_host::prune_retired();
+  VR_ENTRY_BEGIN(h, a)
   // the image and, behind it, the aux plane in the handle's output buffer
   const size_t plane = (size_t)a->resolution[0] * (size_t)a->resolution[1] * sizeof(float);
   const size_t bytes = 4 * plane;
   if (plane && !out) return fail(VR_ERR_ARGUMENT, "output is NULL");
-  if (bytes > h->d_out_bytes) {
-    if (h->d_out) VR_HIP(hipFree(h->d_out));
-    h->d_out = nullptr;
-    h->d_out_bytes = 0;
-    VR_HIP(hipMalloc(&h->d_out, bytes));
-    h->d_out_bytes = bytes;
-  }
+  ensure_out(h, bytes);
   float *d_aux = out_aux ? h->d_out + 3 * (plane / sizeof(float)) : nullptr;
   const int rc = do_project(h, a, mode, nullptr, h->d_out, d_aux, nullptr, nullptr);
   if (rc) return rc;
@@ -3280,11 +3235,7 @@ int vr_render_slice_device(vr_context *h, const vr_slice *s, float *d_out, float
                            void *stream) {
   std::lock_guard<std::mutex> lk(g_mu);
   if (int rc = check_slice(s)) return rc;
-  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
-  if (!h->children.empty()) return fail(VR_ERR_UNSUPPORTED, "vr_render_slice_device: one-device handles only");
-  VR_GUARD_BEGIN
-  DeviceGuard dg(h->device);
-  vr_host::prune_retired();
+  VR_ENTRY_BEGIN(h, s)
   return do_slice(h, s, d_out, d_aux, d_labels, (hipStream_t)stream);
   VR_GUARD_END
 }
@@ -3292,23 +3243,13 @@ int vr_render_slice_device(vr_context *h, const vr_slice *s, float *d_out, float
 int vr_render_slice(vr_context *h, const vr_slice *s, float *out, float *out_aux, float *out_labels) {
   std::lock_guard<std::mutex> lk(g_mu);
   if (int rc = check_slice(s)) return rc;
-  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
-  if (!h->children.empty()) return fail(VR_ERR_UNSUPPORTED, "vr_render_slice: one-device handles only");
-  VR_GUARD_BEGIN
-  DeviceGuard dg(h->device);
-  vr_host::prune_retired();
+  VR_ENTRY_BEGIN(h, s)
   // up to three planes in the handle's output buffer: the image, aux, labels
   const size_t count = (size_t)s->resolution[0] * (size_t)s->resolution[1];
   const size_t plane = count * sizeof(float);
   const size_t bytes = 3 * plane;
   if (plane && !out) return fail(VR_ERR_ARGUMENT, "output is NULL");
-  if (bytes > h->d_out_bytes) {
-    if (h->d_out) VR_HIP(hipFree(h->d_out));
-    h->d_out = nullptr;
-    h->d_out_bytes = 0;
-    VR_HIP(hipMalloc(&h->d_out, bytes));
-    h->d_out_bytes = bytes;
-  }
+  ensure_out(h, bytes);
   float *d_aux = out_aux ? h->d_out + count : nullptr;
   float *d_lab = out_labels ? h->d_out + 2 * count : nullptr;
   const int rc = do_slice(h, s, h->d_out, d_aux, d_lab, nullptr);
@@ -3412,12 +3353,7 @@ int vr_render_isosurface_device(vr_context *h, const vr_render_args *a, float le
                                 void *stream) {
   std::lock_guard<std::mutex> lk(g_mu);
   if (level != level) return fail(VR_ERR_ARGUMENT, "isosurface level is NaN");
-  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
-  if (!a) return fail(VR_ERR_ARGUMENT, "insufficient parameter!");
-  if (!h->children.empty()) return fail(VR_ERR_UNSUPPORTED, "vr_render_isosurface_device: one-device handles only");
-  VR_GUARD_BEGIN
-  DeviceGuard dg(h->device);
-  vr_host::prune_retired();
+  VR_ENTRY_BEGIN(h, a)
   return do_isosurface(h, a, level, part, d_out, d_depth, d_normal, d_steps, (hipStream_t)stream);
   VR_GUARD_END
 }
@@ -3426,23 +3362,12 @@ int vr_render_isosurface(vr_context *h, const vr_render_args *a, float level, fl
                          float *out_normal) {
   std::lock_guard<std::mutex> lk(g_mu);
   if (level != level) return fail(VR_ERR_ARGUMENT, "isosurface level is NaN");
-  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
-  if (!a) return fail(VR_ERR_ARGUMENT, "insufficient parameter!");
-  if (!h->children.empty()) return fail(VR_ERR_UNSUPPORTED, "vr_render_isosurface: one-device handles only");
-  VR_GUARD_BEGIN
-  DeviceGuard dg(h->device);
-  vr_host::prune_retired();
+  VR_ENTRY_BEGIN(h, a)
   // the image and, behind it, the depth plane and the three normal planes in the handle's output buffer
   const size_t plane = (size_t)a->resolution[0] * (size_t)a->resolution[1] * sizeof(float);
   const size_t bytes = 7 * plane;
   if (plane && !out) return fail(VR_ERR_ARGUMENT, "output is NULL");
-  if (bytes > h->d_out_bytes) {
-    if (h->d_out) VR_HIP(hipFree(h->d_out));
-    h->d_out = nullptr;
-    h->d_out_bytes = 0;
-    VR_HIP(hipMalloc(&h->d_out, bytes));
-    h->d_out_bytes = bytes;
-  }
+  ensure_out(h, bytes);
   float *d_depth = out_depth ? h->d_out + 3 * (plane / sizeof(float)) : nullptr;
   float *d_normal = out_normal ? h->d_out + 4 * (plane / sizeof(float)) : nullptr;
   const int rc = do_isosurface(h, a, level, nullptr, h->d_out, d_depth, d_normal, nullptr, nullptr);
@@ -3458,12 +3383,7 @@ int vr_render_transfer_device(vr_context *h, const vr_render_args *a, const vr_t
                               float *d_out, float *d_alpha, unsigned long long *d_steps, void *stream) {
   std::lock_guard<std::mutex> lk(g_mu);
   if (int rc = check_transfer(tf)) return rc;
-  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
-  if (!a) return fail(VR_ERR_ARGUMENT, "insufficient parameter!");
-  if (!h->children.empty()) return fail(VR_ERR_UNSUPPORTED, "vr_render_transfer_device: one-device handles only");
-  VR_GUARD_BEGIN
-  DeviceGuard dg(h->device);
-  vr_host::prune_retired();
+  VR_ENTRY_BEGIN(h, a)
   return do_transfer(h, a, tf, part, d_out, d_alpha, d_steps, (hipStream_t)stream);
   VR_GUARD_END
 }
@@ -3471,23 +3391,12 @@ int vr_render_transfer_device(vr_context *h, const vr_render_args *a, const vr_t
 int vr_render_transfer(vr_context *h, const vr_render_args *a, const vr_transfer *tf, float *out, float *out_alpha) {
   std::lock_guard<std::mutex> lk(g_mu);
   if (int rc = check_transfer(tf)) return rc;
-  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
-  if (!a) return fail(VR_ERR_ARGUMENT, "insufficient parameter!");
-  if (!h->children.empty()) return fail(VR_ERR_UNSUPPORTED, "vr_render_transfer: one-device handles only");
-  VR_GUARD_BEGIN
-  DeviceGuard dg(h->device);
-  vr_host::prune_retired();
+  VR_ENTRY_BEGIN(h, a)
   // the image and, behind it, the alpha plane in the handle's output buffer
   const size_t plane = (size_t)a->resolution[0] * (size_t)a->resolution[1] * sizeof(float);
   const size_t bytes = 4 * plane;
   if (plane && !out) return fail(VR_ERR_ARGUMENT, "output is NULL");
-  if (bytes > h->d_out_bytes) {
-    if (h->d_out) VR_HIP(hipFree(h->d_out));
-    h->d_out = nullptr;
-    h->d_out_bytes = 0;
-    VR_HIP(hipMalloc(&h->d_out, bytes));
-    h->d_out_bytes = bytes;
-  }
+  ensure_out(h, bytes);
   float *d_alpha = out_alpha ? h->d_out + 3 * (plane / sizeof(float)) : nullptr;
   const int rc = do_transfer(h, a, tf, nullptr, h->d_out, d_alpha, nullptr, nullptr);
   if (rc) return rc;

@@ -6,11 +6,12 @@
 // clamped to 0, t += tstep, pos += step, the max_steps cap), with no opacity exit, and stops a ray at
 // its first sample k with v_k >= level (a NaN sample is never >=).  One lane per ray.
 //
-// Search: the projection kernel's loop -- positions and row loads of VR_ISO_BATCH consecutive samples
-// first, then the fold in sample order.  A lane that hits keeps pos_{k-1} and t_{k-1} (the position
+// Search: the loop of the one-lane feature kernels, built from vr_raycast.h (pixel, ray start, emission
+// sampler, recurrence, probe) -- positions and row loads of VR_ISO_BATCH consecutive samples first, then
+// the fold in sample order.  A lane that hits keeps pos_{k-1} and t_{k-1} (the position
 // and t of the last sample below the level) and goes dead; the wave leaves the loop on !__any(alive).
 //
-// Empty-space leap (PROBE): probe_run / leap as the projection kernel, launched only for level > 0: a
+// Empty-space leap (PROBE): the probe of vr_raycast.h (probe_step), launched only for level > 0: a
 // leaped run's samples are +-0 and cannot reach a positive level.  The run is replayed as ps - 1
 // samples and one more, so that a ray whose first sample after the run hits knows pos_{k-1}.
 //
@@ -23,10 +24,7 @@
 #include <math.h>
 #include <type_traits>
 
-#include "vr_clip.h"
-#include "vr_device.h"
-#include "vr_sampling.h"
-#include "vr_stage.h"
+#include "vr_raycast.h"
 
 #ifndef VR_ISO_REFINE
 #define VR_ISO_REFINE 6  // bisection steps between the last sample below the level and the hit (vrhip.h)
@@ -43,21 +41,14 @@
 
 namespace vr {
 
-// The launch arguments that are not RenderParams (which must not grow, vr_device.h): the level, the
-// depth plane -- [plane_cols][H] as one plane of the image, or null -- and the normal planes --
-// [3][plane_cols][H] as the image, or null.
+// The launch arguments that are not RenderParams (Args, vr_raycast.h): the level, the depth plane --
+// [plane_cols][H] as one plane of the image, or null -- and the normal planes -- [3][plane_cols][H] as
+// the image, or null.
 struct IsoExtras {
   float level;
   float *depth;
   float *normal;
 };
-// The same for a clipped instantiation, with the plane set (vr_clip.h).  The unclipped kernels keep
-// the arguments they had before there were planes.
-struct IsoExtrasClip : IsoExtras {
-  ClipSet clip;
-};
-template <bool CLIP>
-using IsoArgs = std::conditional_t<CLIP, IsoExtrasClip, IsoExtras>;
 
 // GRAD 1: on-the-fly gradient (six taps of the gem binding), 2: lookup (gx, gy, gz).
 // COUNT: steps[0] += search samples visited (leaped ones included), steps[1] += search samples
@@ -65,35 +56,21 @@ using IsoArgs = std::conditional_t<CLIP, IsoExtrasClip, IsoExtras>;
 // CLIP: the clip planes shorten [tnear, tfar] after ray_setup.  A hit at the first sample is then the
 // surface point itself (k = 0): the plane cuts the object as the box face does, a capped cut face.
 template <int GRAD, bool BIG, bool PROBE, bool COUNT, bool CLIP>
-__global__ __launch_bounds__(256) void isosurface_kernel(const RenderParams P, const IsoArgs<CLIP> X) {
-  // tile and lane mapping of project_kernel / render_kernel
+__global__ __launch_bounds__(256) void isosurface_kernel(const RenderParams P, const Args<IsoExtras, CLIP> X) {
   int tx, ty;
   if (!tile_of_block(P, tx, ty)) return;  // whole workgroup: uniform
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lc = tx * 16 + (wave & 1) * 8 + (lane >> 3);  // local (partition) column
-  const int y = ty * 16 + (wave >> 1) * 8 + (lane & 7);
-  const bool active = (lc < P.part_cols) && (y < P.height);
+  const Pixel px = pixel_of_tile(P, tx, ty);
+  const int lane = px.lane;
   const f3 bmin = mk(P.bmin[0], P.bmin[1], P.bmin[2]);
   const f3 bsc = mk(P.bscale[0], P.bscale[1], P.bscale[2]);
   const float tstep = P.tstep, level = X.level;
 
-  bool hit = false;
-  float t = 0.f, tfar = 0.f;
-  f3 pos = bmin, step = mk(0.f, 0.f, 0.f);  // (a lane without a ray samples the box corner, untested)
-  if (active) {
-    const int blk = lc / P.block_cols, within = lc - blk * P.block_cols;
-    const int x = (P.part + blk * P.num_parts) * P.block_cols + within;
-    f3 o, d;
-    float tnear;
-    hit = ray_setup(P, x, y, o, d, tnear, tfar);  // volumeRender_kernel.cu:388-425
-    if constexpr (CLIP) hit = clip_interval(X.clip, o, d, hit, tnear, tfar);
-    if (hit) {
-      pos = mk(fmaf(d.x, tnear, o.x), fmaf(d.y, tnear, o.y), fmaf(d.z, tnear, o.z));
-      step = mk(d.x * tstep, d.y * tstep, d.z * tstep);
-      t = tnear;
-    }
-  }
-  bool alive = hit;
+  const RayStart r = ray_start<CLIP>(P, X, px.active, px.lc, px.y, bmin, tstep);
+  const float tfar = r.tfar;
+  const f3 step = r.step;
+  float t = r.t;
+  f3 pos = r.pos;
+  bool alive = r.hit;
   int32_t nsteps = 0, nfetch = 0;
   // the search's result: found -- sample k reached the level; first -- k == 0; (bpos, bt) -- the
   // position and t of sample k - 1 (of sample 0 when first); (qpos, qt) -- those of the lane's last
@@ -102,56 +79,22 @@ __global__ __launch_bounds__(256) void isosurface_kernel(const RenderParams P, c
   f3 bpos = bmin, qpos = bmin;
   float bt = 0.f, qt = 0.f;
 
-  // the emission texture's state, wave-uniform: 0 unbound (reads 0), 1 a single voxel, 2 a grid
-  const int kind = P.em.p == nullptr ? 0 : (P.em.one ? 1 : 2);
-  float one = 0.f;
-  if (kind == 1) {
-    const float q = P.em.p[0];
-    one = fmaf(0.5f, q - q, q);  // == lerp(q, q, w) for every w (tex3d)
-  }
-  // the emission sample at world position p (in bounds for any p: axis() clamps every index)
-  auto em_at = [&](const f3 &p) __attribute__((always_inline)) {
-    if (kind != 2) return one;
-    const f3 q = mk((p.x - bmin.x) * bsc.x, (p.y - bmin.y) * bsc.y, (p.z - bmin.z) * bsc.z);
-    return fetch<BIG>(P.em, axis(q.x, P.em.nx, P.em.fnx), axis(q.y, P.em.ny, P.em.fny),
-                      axis(q.z, P.em.nz, P.em.fnz));
-  };
-
-  // Empty-space probe, as project_kernel: ps > 0 -- the next probe's run length; -1 -- a probe found
-  // data: re-armed by an all-zero batch after `rest` batches; 0 -- never probed.
-  int ps = 0, rest = 0;
-  KParams kp = nullptr;
-  if constexpr (PROBE) {
-    kp = (KParams)__builtin_amdgcn_kernarg_segment_ptr();
-    const bool fin = fabsf(pos.x) < INFINITY && fabsf(pos.y) < INFINITY && fabsf(pos.z) < INFINITY &&
-                     fabsf(step.x) < INFINITY && fabsf(step.y) < INFINITY && fabsf(step.z) < INFINITY &&
-                     fabsf(t) < INFINITY;
-    if (kind == 2 && tstep > 0.f && tstep < INFINITY && __all(!alive || fin)) ps = VR_ISO_PROBE_MIN;
-  }
+  const Emission em = emission_of(P);
+  Probe prb;
+  if constexpr (PROBE) prb = probe_arm<VR_ISO_PROBE_MIN>(em.kind, tstep, alive, pos, step, t);
 
   while (__any(alive)) {
     if constexpr (PROBE) {
-      if (ps > 0) {
-        int e = probe_run(P, kp, alive, pos, step, t, tfar, ps, lane);
-        // an occupied (or too large) box: runs half as long until one is empty or the shortest fails
-        while (e <= 0 && ps > VR_ISO_PROBE_MIN) {
-          ps >>= 1;
-          e = probe_run(P, kp, alive, pos, step, t, tfar, ps, lane);
+      // the run's samples are +-0 < level: none hits.  The last of them is a live ray's k - 1.
+      const auto on_empty = [&](int ps) __attribute__((always_inline)) {
+        leap(P, ps - 1, alive, nsteps, t, tfar, pos, step);
+        if (alive) {
+          qpos = pos;
+          qt = t;
         }
-        if (e > 0) {
-          // the run's samples are +-0 < level: none hits.  The last of them is a live ray's k - 1.
-          leap(P, ps - 1, alive, nsteps, t, tfar, pos, step);
-          if (alive) {
-            qpos = pos;
-            qt = t;
-          }
-          leap(P, 1, alive, nsteps, t, tfar, pos, step);
-          ps = min(2 * ps, (int)VR_PROBE_MAX);
-          continue;
-        }
-        ps = -1;  // off until re-armed
-        rest = VR_ISO_PROBE_REST;
-      }
+        leap(P, 1, alive, nsteps, t, tfar, pos, step);
+      };
+      if (probe_step<VR_ISO_PROBE_MIN, VR_ISO_PROBE_REST>(P, prb, alive, pos, step, t, tfar, lane, on_empty)) continue;
     }
     // ---- a batch: positions and loads of VR_ISO_BATCH consecutive samples, then the fold -------
     float v[VR_ISO_BATCH], tt[VR_ISO_BATCH];
@@ -164,24 +107,11 @@ __global__ __launch_bounds__(256) void isosurface_kernel(const RenderParams P, c
         lv[j] = alive;
         tt[j] = t;
         pp[j] = pos;
-        if constexpr (decltype(grid)::value) {
-          const f3 q = mk((pos.x - bmin.x) * bsc.x, (pos.y - bmin.y) * bsc.y, (pos.z - bmin.z) * bsc.z);
-          v[j] = fetch<BIG>(P.em, axis(q.x, P.em.nx, P.em.fnx), axis(q.y, P.em.ny, P.em.fny),
-                            axis(q.z, P.em.nz, P.em.fnz));
-        } else {
-          v[j] = one;  // (unbound: 0)
-        }
-        // the march recurrences of render_kernel: ++n, the cap, t += tstep, the exit test, pos += step
-        const int32_t n1 = nsteps + 1;
-        const float t1 = t + tstep;
-        const bool go = alive && n1 < P.max_steps && !(t1 > tfar);
-        nsteps = alive ? n1 : nsteps;
-        t = alive ? t1 : t;
-        pos = go ? mk(pos.x + step.x, pos.y + step.y, pos.z + step.z) : pos;
-        alive = go;
+        v[j] = em_at<BIG>(P, grid, em.one, bmin, bsc, pos);
+        next_sample(P, tstep, tfar, step, alive, nsteps, t, pos);
       }
     };
-    if (kind == 2) batch(std::true_type{});
+    if (em.kind == 2) batch(std::true_type{});
     else batch(std::false_type{});
     bool nz = false;
 #pragma unroll
@@ -202,12 +132,7 @@ __global__ __launch_bounds__(256) void isosurface_kernel(const RenderParams P, c
       }
     }
     alive = alive && !found;
-    if constexpr (PROBE) {
-      if (ps < 0) {
-        if (rest > 0) --rest;
-        else if (!__any(nz)) ps = VR_ISO_PROBE_MIN;  // back in empty space: probe again
-      }
-    }
+    if constexpr (PROBE) probe_rearm<VR_ISO_PROBE_MIN>(prb, nz);
   }
 
   // ---- the surface sample: once per lane, under the lane's mask -------------------------------------
@@ -220,15 +145,16 @@ __global__ __launch_bounds__(256) void isosurface_kernel(const RenderParams P, c
 #pragma unroll 1
     for (int i = 0; i < VR_ISO_REFINE; ++i) {
       const float c = (lo + hi) * 0.5f;  // exact
-      const float vc = em_at(mk(fmaf(step.x, c, bpos.x), fmaf(step.y, c, bpos.y), fmaf(step.z, c, bpos.z)));
+      const f3 pc = mk(fmaf(step.x, c, bpos.x), fmaf(step.y, c, bpos.y), fmaf(step.z, c, bpos.z));
+      const float vc = em_at<BIG>(P, em.kind, em.one, bmin, bsc, pc);
       if (vc >= level) hi = c;
       else lo = c;
     }
     // hi = 1 gives pos_k and t_k bit for bit; k = 0: the first sample itself (the box face cuts the object)
     const f3 p = first ? bpos : mk(fmaf(step.x, hi, bpos.x), fmaf(step.y, hi, bpos.y), fmaf(step.z, hi, bpos.z));
     const float tsur = first ? bt : fmaf(tstep, hi, bt);
-    const f3 s = mk((p.x - bmin.x) * bsc.x, (p.y - bmin.y) * bsc.y, (p.z - bmin.z) * bsc.z);
-    const float vs = em_at(p);
+    const f3 s = tex_coord(bmin, bsc, p);
+    const float vs = em_at<BIG>(P, em.kind, em.one, bmin, bsc, p);
     // the gradient render's exact shading takes (render_kernel without SHARE: the oracle's expressions)
     f3 g;
     if (GRAD == 1) {
@@ -262,10 +188,8 @@ __global__ __launch_bounds__(256) void isosurface_kernel(const RenderParams P, c
     }
   }
 
-  if (active) {
-    // column-major planar output of this partition (render_kernel); depth and normal likewise
-    const size_t plane = (size_t)P.plane_cols * (size_t)P.height;
-    const size_t k = (size_t)lc * (size_t)P.height + (size_t)y;
+  if (px.active) {
+    const size_t plane = px.plane(P), k = px.k(P);  // depth and normal as planes of the image
     P.out[k] = pr;
     P.out[k + plane] = pg;
     P.out[k + 2 * plane] = pb;
@@ -277,40 +201,13 @@ __global__ __launch_bounds__(256) void isosurface_kernel(const RenderParams P, c
     }
   }
   if (COUNT) {
-    unsigned long long sv = (unsigned long long)nsteps, sf = (unsigned long long)nfetch;
-    unsigned long long sn = found ? 1ull : 0ull;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      sv += __shfl_xor(sv, off, 64);
-      sf += __shfl_xor(sf, off, 64);
-      sn += __shfl_xor(sn, off, 64);
-    }
-    if (lane == 0 && sv) atomicAdd(P.steps, sv);
-    if (lane == 0 && sf) atomicAdd(P.steps + 1, sf);
-    if (lane == 0 && sn) atomicAdd(P.steps + 2, sn);
+    unsigned long long c[3] = {(unsigned long long)nsteps, (unsigned long long)nfetch, found ? 1ull : 0ull};
+    add_steps(P.steps, lane, c);
   }
 }
 
 // ------------------------------------------------------------------------------------------------
 // launch helper (called from vr_capi.hip)
-
-template <int GRAD, bool BIG, bool PROBE, bool CLIP>
-static void launch_k(const RenderParams &P, const IsoArgs<CLIP> &X, dim3 grid, hipStream_t s) {
-  if (P.steps) hipLaunchKernelGGL((isosurface_kernel<GRAD, BIG, PROBE, true, CLIP>), grid, dim3(256), 0, s, P, X);
-  else hipLaunchKernelGGL((isosurface_kernel<GRAD, BIG, PROBE, false, CLIP>), grid, dim3(256), 0, s, P, X);
-}
-
-template <int GRAD, bool BIG, bool PROBE>
-static void launch_c(const RenderParams &P, const IsoExtrasClip &X, dim3 grid, hipStream_t s) {
-  if (X.clip.n > 0) launch_k<GRAD, BIG, PROBE, true>(P, X, grid, s);
-  else launch_k<GRAD, BIG, PROBE, false>(P, static_cast<const IsoExtras &>(X), grid, s);
-}
-
-template <int GRAD>
-static void launch_g(const RenderParams &P, const IsoExtrasClip &X, bool big, bool probe, dim3 grid, hipStream_t s) {
-  if (big) probe ? launch_c<GRAD, true, true>(P, X, grid, s) : launch_c<GRAD, true, false>(P, X, grid, s);
-  else probe ? launch_c<GRAD, false, true>(P, X, grid, s) : launch_c<GRAD, false, false>(P, X, grid, s);
-}
 
 // grad: 1 on-the-fly, 2 lookup; probe: leap empty space (needs P.occ and a level above 0); clip: the
 // launch's plane set, or null / n == 0: the unclipped instantiations
@@ -318,16 +215,21 @@ hipError_t launch_isosurface(const RenderParams &P, int grad, float level, float
                              bool probe, hipStream_t s, const ClipSet *clip) {
   if (P.part_cols <= 0 || P.height <= 0) return hipSuccess;
   if (grad != 1 && grad != 2) return hipErrorInvalidValue;
-  const uint64_t ntx = (P.part_cols + 15) / 16, nty = (P.height + 15) / 16;
-  const dim3 grid((unsigned)(ntx * nty));  // (tile_mode 0: row-major tiles)
-  IsoExtrasClip X{};
+  WithClip<IsoExtras> X{};
   X.level = level;
   X.depth = depth;
   X.normal = normal;
   if (clip) X.clip = *clip;
   probe = probe && P.occ != nullptr && P.occ_bx != 0u && level > 0.f;
-  if (grad == 1) launch_g<1>(P, X, big, probe, grid, s);
-  else launch_g<2>(P, X, big, probe, grid, s);
+  with_bools(
+      [&](auto big, auto probe, auto count, auto clipped) {
+        constexpr bool B = decltype(big)::value, PR = decltype(probe)::value, C = decltype(count)::value,
+                       CL = decltype(clipped)::value;
+        const Args<IsoExtras, CL> &A = X;
+        if (grad == 1) hipLaunchKernelGGL((isosurface_kernel<1, B, PR, C, CL>), tile_grid(P), dim3(256), 0, s, P, A);
+        else hipLaunchKernelGGL((isosurface_kernel<2, B, PR, C, CL>), tile_grid(P), dim3(256), 0, s, P, A);
+      },
+      big, probe, P.steps != nullptr, X.clip.n > 0);
   return hipGetLastError();
 }
 
