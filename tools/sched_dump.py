@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Summarise a VR_SCHED_DUMP file (block durations of timed launches, vr_capi.hip).
+"""Summarise a VR_SCHED_DUMP file (block durations of timed launches, vr_render.hip do_render).
 
 Each record: uint32 header (K, part, num_parts, blocks) then `blocks` uint32 durations in
 s_memrealtime ticks (100 MHz).  A block split inside its workgroup (SCHED 5) records twice its

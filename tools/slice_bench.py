@@ -69,7 +69,7 @@ def lines_per_wave(s, dims, lanes_x, waves=192):
 
 
 def rule_lanes_x(s, dims, planes):
-    """The host's lane-axis rule (vr_capi.hip slice_lanes_x), restated."""
+    """The host's lane-axis rule (vr_features.hip slice_lanes_x), restated."""
     _, du, dv, _ = geometry(s)
     d = np.array(dims, np.float64)
 

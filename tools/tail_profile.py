@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """tools/tail_profile.py DUMP [slots] -- occupancy profile of timed march launches from a
 VR_SCHED_DUMP run (DUMP: block durations, DUMP.start: block start ticks, both in s_memrealtime
-ticks of 10 ns; written by vr_capi.hip do_render).  For each launch: span, the resident-workgroup
+ticks of 10 ns; written by vr_render.hip do_render).  For each launch: span, the resident-workgroup
 count over time, how long the launch runs below 90 % / 50 % of its peak residency (the ramp-down
 tail), and the idle fraction of the workgroup slots over the span."""
 import json

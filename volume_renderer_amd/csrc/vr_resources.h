@@ -1,4 +1,4 @@
-// vr_resources.h -- device-resource lifetime of libvrhip's host driver (included by vr_capi.hip only).
+// vr_resources.h -- device-resource lifetime of libvrhip's host driver (included by the host files through vr_host.h).
 //
 // The reference serialises everything on CUDA's legacy default stream: an upload or a texture
 // rebind can never overlap a render (volumeRender_kernel.cu:551-722 bind/copy synchronously, the
@@ -364,9 +364,9 @@ inline std::map<int, ConstRing> &rings() {
 }
 
 // What one launch reads: its buffers' owners are kept alive, and marked with the launch's event by
-// finish(); the staged constants' ring slot is released by the same event.
+// finish(); the staged constants' ring slot is released by the same event.  (vr_host.h: LaunchRec, of BufPtr)
 template <class BufPtrT>
-struct LaunchRec {
+struct LaunchRecOf {
   hipStream_t stream = nullptr;
   int device = 0;
   std::vector<BufPtrT> reads;
