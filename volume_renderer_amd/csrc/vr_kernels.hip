@@ -35,7 +35,7 @@ namespace vr {
 // gradient taps (MODE 1) / all axes of the lookups (MODE 2) are the centre sample's.
 // CLIP: the handle's clip planes shorten [tnear, tfar] after ray_setup (vr_clip.h); C is empty otherwise.
 template <int MODE, bool AB_ALIAS, bool BIG, bool COUNT, bool SHARE, bool FAST, bool CLIP>
-__global__ __launch_bounds__(256, VR_MIN_WAVES) void render_kernel(const RenderParams P, const ClipArg<CLIP> C) {
+__global__ __launch_bounds__(256, 1) void render_kernel(const RenderParams P, const ClipArg<CLIP> C) {
   // 16x16 pixel workgroup tile; wave w owns the 8x8 quadrant (w & 1, w >> 1); lane -> (x, y)
   // with y fastest so that the column-major output stores of a lane octet are contiguous.
   int tx, ty;
@@ -406,34 +406,30 @@ hipError_t launch_gradient(const float *d, const uint64_t dims[3], float *gx, fl
   return hipGetLastError();
 }
 
-// out[e] = (a, b, c, 0) of padded voxel e: rows of the padded volume, or (VR_GVEC_BRICK) 2x2x2
-// bricks, entry ((Z/2 * by + Y/2) * bx + X/2) * 8 + (X&1) + 2 (Y&1) + 4 (Z&1) (vr_sampling.h
-// fetch_vec), the bricks past an odd padded edge zero-filled.
+// out[e] = (a, b, c, 0) of a padded voxel, in 2x2x2 bricks: voxel (X, Y, Z) is entry
+// ((Z/2 * by + Y/2) * bx + X/2) * 8 + (X&1) + 2 (Y&1) + 4 (Z&1) (vr_sampling.h fetch_vec), the
+// bricks past an odd padded edge zero-filled.
 __global__ __launch_bounds__(256) void interleave3_kernel(const float *__restrict__ a, const float *__restrict__ b,
                                                           const float *__restrict__ c, float4 *__restrict__ out,
                                                           uint64_t n, uint32_t px, uint32_t py, uint32_t pz) {
   const uint32_t bx = (px + 1) >> 1, by = (py + 1) >> 1;
   for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    uint64_t src = i;
-    if (VR_GVEC_BRICK) {
-      const uint64_t brick = i >> 3, e = i & 7u;
-      const uint64_t bz = brick / ((uint64_t)bx * by), rem = brick - bz * bx * by;
-      const uint32_t byi = (uint32_t)(rem / bx), bxi = (uint32_t)(rem - (uint64_t)byi * bx);
-      const uint32_t X = 2u * bxi + (uint32_t)(e & 1u), Y = 2u * byi + (uint32_t)((e >> 1) & 1u);
-      const uint64_t Z = 2u * bz + (e >> 2);
-      if (X >= px || Y >= py || Z >= pz) {
-        out[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        continue;
-      }
-      src = (Z * py + Y) * px + X;
+    const uint64_t brick = i >> 3, e = i & 7u;
+    const uint64_t bz = brick / ((uint64_t)bx * by), rem = brick - bz * bx * by;
+    const uint32_t byi = (uint32_t)(rem / bx), bxi = (uint32_t)(rem - (uint64_t)byi * bx);
+    const uint32_t X = 2u * bxi + (uint32_t)(e & 1u), Y = 2u * byi + (uint32_t)((e >> 1) & 1u);
+    const uint64_t Z = 2u * bz + (e >> 2);
+    if (X >= px || Y >= py || Z >= pz) {
+      out[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      continue;
     }
+    const uint64_t src = (Z * py + Y) * px + X;
     out[i] = make_float4(a[src], b[src], c[src], 0.f);
   }
 }
 
 // Entries of the interleaved lookup gradient of a padded px x py x pz volume.
 uint64_t interleave3_entries(uint32_t px, uint32_t py, uint32_t pz) {
-  if (!VR_GVEC_BRICK) return (uint64_t)px * py * pz;
   return 8ull * ((px + 1) >> 1) * ((py + 1) >> 1) * ((pz + 1) >> 1);
 }
 

@@ -22,28 +22,13 @@
 #ifndef VR_MARCH_K
 #define VR_MARCH_K 1  // depth lanes of this object file (see below)
 #endif
-#ifndef VR_MERGED_BOUNDS
-#define VR_MERGED_BOUNDS 1  // one wave-uniform slot test for the centre and the half-texel taps
-#endif
-#ifndef VR_WHOLE_BOX
-// 1: in a chunk whose whole tap box is staged (not partial; tame waves, not a slab), every tap of
-// every sample lies in the box by construction (plan_chunk: the box of all taps of the live rays'
-// next S samples, the drift of the rounded position additions in its halo), so the per-sample
-// merged slot test is not evaluated.  VR_CHECK_WHOLE=1 (diagnostic build): evaluated anyway, and a
-// sample it fails is reported with printf.
-#define VR_WHOLE_BOX 1
-#endif
 #ifndef VR_CHECK_WHOLE
+// In a chunk whose whole tap box is staged (not partial; tame waves, not a slab), every tap of every
+// sample lies in the box by construction (plan_chunk: the box of all taps of the live rays' next S
+// samples, the drift of the rounded position additions in its halo), so the per-sample slot test of
+// the half-texel tap launch is not evaluated (sample_at).  VR_CHECK_WHOLE=1 (diagnostic build):
+// evaluated anyway, and a sample it fails is reported with printf.
 #define VR_CHECK_WHOLE 0
-#endif
-#ifndef VR_LIGHTS_HOIST
-#define VR_LIGHTS_HOIST 1  // tame launches: the first light pair held in registers across the march
-#endif
-#ifndef VR_REFL_HOIST
-#define VR_REFL_HOIST 1  // tame launches: the reflection's single voxel read once per wave (sample_at)
-#endif
-#ifndef VR_ADAPTIVE_S
-#define VR_ADAPTIVE_S 1
 #endif
 #ifndef VR_WHOLE_SPLIT
 #define VR_WHOLE_SPLIT 1  // K > 1: the sample loop compiled twice, for whole chunks and the others
@@ -56,9 +41,6 @@
 #endif
 #if VR_CHECK_WHOLE
 static __device__ unsigned long long vr_whole_violations;  // (diagnostic build) samples the whole-box rule misses
-#endif
-#ifndef VR_BRANCHFREE_LEAP
-#define VR_BRANCHFREE_LEAP 1  // empty-chunk leap of K = 1 lanes without per-step branches
 #endif
 #ifndef VR_CHUNK_PER_LANE
 #define VR_CHUNK_PER_LANE 16  // chunk length per depth lane for K >= 2 (samples per ray per chunk)
@@ -159,39 +141,15 @@ struct ChunkStats {
   uint32_t staged, leap, fall, iter, lit, probe, probe_fail;
 };
 
-#ifndef VR_CUBE_AXIS
-#define VR_CUBE_AXIS 1  // the half-texel tap launch forms its axes as axis_cube_s (2 VALU instead of 4 per axis)
-#endif
-#ifndef VR_PROBE
-#define VR_PROBE 1  // the empty-space probe (vr_stage.h probe_run); 0: staged empty-chunk leaps only
-#endif
-#ifndef VR_NL2
-#define VR_NL2 1  // round 6: the two-light march specialised (march_kernel, shade_fast NL)
-#endif
-#ifndef VR_PARK
-#define VR_PARK 1  // round 6: wave-front alignment of rays far apart along their direction (march)
-#endif
 #ifndef VR_PARK_SAMPLES
-#define VR_PARK_SAMPLES (2 * VR_CHUNK)  // parked: more than this many steps ahead of the wave's hindmost ray
-#endif
-#ifndef VR_REPROBE_PARTIAL
-#define VR_REPROBE_PARTIAL 1  // after a partial chunk the probe runs again before the next chunk
-#endif
-#ifndef VR_PRELEAP
-#define VR_PRELEAP 1  // round 6: per-lane leaps of empty runs before the march of a wave whose rays are far apart
+// wave-front alignment (round 6, march): a ray more than this many steps ahead of the wave's hindmost
+// ray is parked
+#define VR_PARK_SAMPLES (2 * VR_CHUNK)
 #endif
 #ifndef VR_PRELEAP_SPREAD
-#define VR_PRELEAP_SPREAD 256  // ... more than this many steps apart (the grazing tiles of rotate(30,10,0): 900-2700)
-#endif
-#ifndef VR_PROBE_LANES
-#define VR_PROBE_LANES 0  // round 6: per-lane probes inside the march loop for waves whose rays are far apart
-                          // (vr_stage.h probe_lanes; measured: +0.4 ms metric, +1.2 ms C3 -- VR_PRELEAP instead)
-#endif
-#ifndef VR_PROBE_BISECT
-// 1: a probe that finds data (or too many bricks) retries at half the run length, down to
-// VR_PROBE_MIN -- the run stops closer to the data (same box: metric 28.4-28.6 -> 27.5 ms, C2 14.6 ->
-// 12.8 ms, P = 8 part 5.27 -> 5.07 ms, r5e)
-#define VR_PROBE_BISECT 1
+// the pre-leap launch (round 6, preleap_kernel) takes a wave whose rays start more than this many steps
+// apart (the grazing tiles of rotate(30,10,0): 900-2700)
+#define VR_PRELEAP_SPREAD 256
 #endif
 #ifndef VR_PROBE_MIN
 #define VR_PROBE_MIN (2 * VR_CHUNK)  // the probe's first run after the march enters empty space
@@ -218,9 +176,10 @@ __device__ __forceinline__ void sample_at(const RenderParams &P, const float *L,
   constexpr bool HALF_ONLY = HALF_TAPS && SHARE2;
   AxS sx{}, sy{}, sz{};
   Ax ax, ay, az;
-  if constexpr (HALF_ONLY && VR_CUBE_AXIS) {
+  if constexpr (HALF_ONLY) {
     // the half-texel tap launch is a power-of-two cube (vr_capi.hip half_texel_taps): the
-    // coordinate in one add and one fma, bit-identical (vr_sampling.h axis_cube_s)
+    // coordinate in one add and one fma, bit-identical (vr_sampling.h axis_cube_s: 2 VALU per axis
+    // instead of 4)
     sx = axis_cube_s<NANCHK>(pos.x, P.cube_hs[0]);
     sy = axis_cube_s<NANCHK>(pos.y, P.cube_hs[1]);
     sz = axis_cube_s<NANCHK>(pos.z, P.cube_hs[2]);
@@ -248,8 +207,7 @@ __device__ __forceinline__ void sample_at(const RenderParams &P, const float *L,
   // most the slot's bytes (< 2^14) -- both factors fit 24 bits and the product 32.  The address is
   // opaque to the compiler, so that every tap is this one register plus a pitch (it otherwise keeps
   // the offset and three copies of the base apart, and adds a base to each of the 14 reads' rows).
-  constexpr bool FOLD =
-      WHOLE_CT && VR_MARCH_FAST && MODE == 1 && SHARE2 && VR_MERGED_BOUNDS && VR_WHOLE_BOX && !VR_CHECK_WHOLE;
+  constexpr bool FOLD = WHOLE_CT && VR_MARCH_FAST && MODE == 1 && SHARE2 && !VR_CHECK_WHOLE;
   const int lx = FOLD ? 0 : slot_coord(ax.i, B.rx), ly = FOLD ? 0 : slot_coord(ay.i, B.ry),
             lz = FOLD ? 0 : slot_coord(az.i, B.rz);
   // (the per-axis box tests, evaluated where used: only the paths that are not wholly staged need them)
@@ -278,8 +236,8 @@ __device__ __forceinline__ void sample_at(const RenderParams &P, const float *L,
   // the centre cell is too (a - 1 >= 0 and a + 1 <= e - 2 put i in [0, e - 2]), so one wave-uniform
   // test serves the centre fetch and the gradient, with no per-lane branch on either
   bool full = false;
-  if constexpr (HALF_ONLY && VR_MERGED_BOUNDS) {
-    if (VR_WHOLE_BOX && !VR_CHECK_WHOLE && whole) {
+  if constexpr (HALF_ONLY) {
+    if (!VR_CHECK_WHOLE && whole) {
       full = true;  // (wave-uniform) a whole box: every tap inside by construction
     } else {
       full = __all(staged && (unsigned)(lx + (sx.hi ? 1 : 0) - 1) < (unsigned)(B.ex - 2) &&
@@ -299,7 +257,7 @@ __device__ __forceinline__ void sample_at(const RenderParams &P, const float *L,
     if (full) em_s = lds_tri_cell(cc, B, ax.w, ay.w, az.w, C);
     else if (staged && inx && iny && inz) em_s = lds_tri_cell(cc, B, ax.w, ay.w, az.w, C);
     else {
-      const DevTex U = reload(E);
+      const DevTex U = E;  // (a copy, as fetch_at's)
       em_s = fetch<BIG>(U, clamp_ax(ax, U.nx), clamp_ax(ay, U.ny), clamp_ax(az, U.nz));
     }
   } else {
@@ -380,7 +338,7 @@ __device__ __forceinline__ void sample_at(const RenderParams &P, const float *L,
     } else if (MODE == 2 && SHARE2) {
       const Ax cx = clamp_ax(ax, E.nx), cy = clamp_ax(ay, E.ny), cz = clamp_ax(az, E.nz);
       if (P.gvec)
-        g = fetch_vec<BIG>(P.gvec, P.gx, P.gv_row8, P.gv_plane8, cx, cy, cz);
+        g = fetch_vec<BIG>(P.gvec, P.gv_row8, P.gv_plane8, cx, cy, cz);
       else
         g = mk(fetch<BIG>(P.gx, cx, cy, cz), fetch<BIG>(P.gy, cx, cy, cz), fetch<BIG>(P.gz, cx, cy, cz));
     } else {
@@ -389,8 +347,8 @@ __device__ __forceinline__ void sample_at(const RenderParams &P, const float *L,
     }
     float refl;
     if constexpr (TAME) {  // the emission sample or the single voxel, selected by a 32-bit mask (v_bfi)
-      // VR_REFL_HOIST: the single voxel loaded once per wave before the march (rv), not per sample
-      const float v = VR_REFL_HOIST ? rv : voxel0(P.re.p);
+      // rv: the single voxel, loaded once per wave before the march (not per sample)
+      const float v = rv;
       const uint32_t m = P.re_mask;
       refl = P.fr * __uint_as_float((__float_as_uint(em_s) & m) | (__float_as_uint(fmaf(0.5f, v - v, v)) & ~m));
     } else {
@@ -429,12 +387,9 @@ __device__ __forceinline__ void composite(const RenderParams &P, Ray &R, float r
 
 // Whether any lane of this lane's K-lane group has b set (called by whole groups).  K = 2, 4: DPP
 // quad_perm swaps within the group (no 64-bit ballot arithmetic); K = 8: the ballot.
-#ifndef VR_GROUP_ANY_DPP
-#define VR_GROUP_ANY_DPP 1
-#endif
 template <int K>
 __device__ __forceinline__ bool group_any(bool b) {
-  if constexpr ((K == 2 || K == 4) && VR_GROUP_ANY_DPP) {
+  if constexpr (K == 2 || K == 4) {
     int v = b ? 1 : 0;
     v |= __builtin_amdgcn_mov_dpp(v, 0xB1, 0xf, 0xf, true);  // quad_perm [1,0,3,2]: lane ^ 1
     if constexpr (K == 4) v |= __builtin_amdgcn_mov_dpp(v, 0x4E, 0xf, 0xf, true);  // [2,3,0,1]: lane ^ 2
@@ -479,9 +434,6 @@ __device__ __forceinline__ int group_max_i(int v, int acc) {
 // exact no-op there: fma(1 - sum.a, 0, s) = s for the finite sums of a tame launch (never -0: they
 // start at +0 and an exact zero sum rounds to +0), and the exit test sees the unchanged sum.a,
 // which a live ray has already passed.  Saves the broadcast and test of exf per group lane.
-#ifndef VR_ZERO_FILL
-#define VR_ZERO_FILL 1
-#endif
 template <int K, int I, bool ZF = false>
 __device__ __forceinline__ void composite_group(const RenderParams &P, Ray &R, bool &alive, float exf, float r, float gg,
                                                 float b, float alpha, float thr) {
@@ -570,7 +522,7 @@ __device__ __forceinline__ void march(const RenderParams &P, float *L, int lane,
     R.alive = group_any<K>(R.mine);
   }
 
-  // VR_ADAPTIVE_S: the first box attempt of a chunk is twice the length the wave's last chunk
+  // s0: the first box attempt of a chunk is twice the length the wave's last chunk
   // staged (its box grows little from one chunk to the next), and the shortest after a partial box,
   // instead of always VR_CHUNK halved until it fits: fewer box reductions per chunk.  The samples
   // are the same whatever the chunk length (the staging never changes a result).
@@ -580,21 +532,21 @@ __device__ __forceinline__ void march(const RenderParams &P, float *L, int lane,
   // off (a probe found data: the staged chunks go on until they find data themselves); -1 -- armed
   // (a chunk found data; the next empty chunk restarts the probe at VR_PROBE_MIN).  Rays start in
   // front of the data, so the probe starts on.
-  constexpr bool PROBE = VR_PROBE && !NANCHK && AB_ALIAS && !SLAB;
+  constexpr bool PROBE = !NANCHK && AB_ALIAS && !SLAB;
   int ps = VR_PROBE_MIN;
   // the tame reflection's single voxel (sample_at), held in a register across the march: an opaque
   // copy, so that the compiler does not re-issue the invariant load in every sample
   float rv = 0.f;
-  if constexpr (!NANCHK && VR_REFL_HOIST) {
+  if constexpr (!NANCHK) {
     if (P.tame && P.re.p) rv = voxel0(P.re.p);
     asm volatile("" : "+v"(rv));
   }
-  // VR_LIGHTS_HOIST: the first light pair likewise (shade_fast), when the frame has two or more
+  // the first light pair likewise (shade_fast), when the frame has two or more
   DevLight pre2[2];
   const DevLight *pre = nullptr;
   // (only where the registers fit without lowering occupancy or spilling: not K = 1, the slab or
   // counter variants, nor the 64-bit, separate-absorption or full-gradient-tap ones)
-  if constexpr (!NANCHK && VR_LIGHTS_HOIST && MODE != 0 && K > 1 && AB_ALIAS && SHARE2 && !BIG && !SLAB && !COUNT) {
+  if constexpr (!NANCHK && MODE != 0 && K > 1 && AB_ALIAS && SHARE2 && !BIG && !SLAB && !COUNT) {
     // (NL = 1: the single light in pre2[0])
     const bool two = NL == 2 || (NL == 0 && P.num_lights >= 2);
     for (int j = 0; j < 2; ++j) {
@@ -608,7 +560,7 @@ __device__ __forceinline__ void march(const RenderParams &P, float *L, int lane,
   // empty probe run); tame waves: one exit test after the n additions (advance_n; t only grows)
   auto leap_run = [&](int n) __attribute__((always_inline)) {
     if constexpr (K == 1) {
-      if (COUNT || !VR_BRANCHFREE_LEAP) leap(P, n, R.alive, R.nsteps, R.t, R.tfar, R.pos, R.step, cap);  // exact counts
+      if (COUNT) leap(P, n, R.alive, R.nsteps, R.t, R.tfar, R.pos, R.step, cap);  // exact counts
       else if constexpr (!NANCHK) advance_n(P, n, R.alive, R.nsteps, R.t, R.tfar, R.pos, R.step, cap);
       else advance(P, n, R.alive, R.nsteps, R.t, R.tfar, R.pos, R.step, cap);
     } else {
@@ -618,7 +570,7 @@ __device__ __forceinline__ void march(const RenderParams &P, float *L, int lane,
     }
   };
   // the state a pre-leap launch left for this wave (preleap_kernel), if any: the rays start there
-  if constexpr (PROBE && VR_PRELEAP && !COUNT) {
+  if constexpr (PROBE && !COUNT) {
     if (kp != nullptr) {
       const KParams kq = kparams_fresh(kp);
       if (kq->pre_flag != nullptr) {
@@ -640,14 +592,14 @@ __device__ __forceinline__ void march(const RenderParams &P, float *L, int lane,
     if constexpr (PROBE) {
       if (ps > 0 && kp != nullptr && kparams_fresh(kp)->occ != nullptr) {
         const bool live = K > 1 ? (R.alive && R.mine) : R.alive;
-        // a box of too many bricks (the wave's rays far apart): each lane's own run (probe_lanes)
+        // (a box of too many bricks -- the wave's rays far apart -- counts as occupied)
         auto probe = [&](int len) __attribute__((always_inline)) {
-          const int r = probe_run(P, kp, live, R.pos, R.step, R.t, R.tfar, len, lane);
-          return (VR_PROBE_LANES && r < 0) ? probe_lanes(P, kp, live, R.pos, R.step, R.t, R.tfar, len) : r;
+          return probe_run(P, kp, live, R.pos, R.step, R.t, R.tfar, len, lane);
         };
         int e = probe(ps);
-        // an occupied (or too large) box: runs half as long until one is empty or the shortest fails
-        while (VR_PROBE_BISECT && e <= 0 && ps > VR_PROBE_MIN) {
+        // an occupied (or too large) box: runs half as long until one is empty or the shortest fails --
+        // the run stops closer to the data
+        while (e <= 0 && ps > VR_PROBE_MIN) {
           ps >>= 1;
           e = probe(ps);
         }
@@ -682,7 +634,7 @@ __device__ __forceinline__ void march(const RenderParams &P, float *L, int lane,
     // held across the sample loop; it has alive = false meanwhile, and every lane of a parked ray's
     // group is parked, so no group operation of the chunk reads it)
     bool parked_any = false;  // wave-uniform
-    if constexpr (VR_PARK && !SLAB && !NANCHK) {
+    if constexpr (!SLAB && !NANCHK) {
       if (!staged || partial) {
         const bool lv = K > 1 ? (R.alive && R.mine) : R.alive;
         // (t >= 0 for every ray: its float bits order as integers)
@@ -706,8 +658,7 @@ __device__ __forceinline__ void march(const RenderParams &P, float *L, int lane,
         R.alive = true;
       }
     };
-    if (VR_ADAPTIVE_S)
-      s0 = (staged && !partial) ? min(2 * S, (int)VR_CHUNK) : (int)(VR_CHUNK >> (VR_ATTEMPTS - 1));
+    s0 = (staged && !partial) ? min(2 * S, (int)VR_CHUNK) : (int)(VR_CHUNK >> (VR_ATTEMPTS - 1));
     bool inside = true;  // slab mode: every sample of this chunk lies in the slab
     if constexpr (SLAB) {
       // a chunk none of whose samples this slab owns is not staged: its samples only replay the
@@ -765,7 +716,7 @@ __device__ __forceinline__ void march(const RenderParams &P, float *L, int lane,
     }
     __builtin_amdgcn_wave_barrier();
     if (COUNT) ++(staged && !partial ? (empty ? C.leap : C.staged) : C.fall);
-    // wave-uniform (sample_at: VR_WHOLE_BOX), held as one scalar rather than a lane mask
+    // wave-uniform (sample_at: a whole box needs no slot test), held as one scalar rather than a lane mask
     const bool whole = __builtin_amdgcn_readfirstlane((!NANCHK && !SLAB && staged && !partial && !edge) ? 1 : 0) != 0;
 
     if (empty) {
@@ -776,10 +727,8 @@ __device__ __forceinline__ void march(const RenderParams &P, float *L, int lane,
       if (PROBE && ps < 0) ps = VR_PROBE_MIN;  // back in empty space after data: probe again
       continue;
     }
-    // data: armed; after a partial chunk (rays far apart, no chunk of theirs can be found empty by
-    // staging) the probe runs again before the next chunk -- one probe costs far less than a chunk of
-    // global gathers (VR_PROBE_LANES)
-    if (PROBE) ps = (VR_PROBE_LANES && VR_REPROBE_PARTIAL && partial) ? (int)VR_PROBE_MIN : -1;
+    // data: armed
+    if (PROBE) ps = -1;
 
     // ---- S samples ---------------------------------------------------------------------------
     if constexpr (K == 1) {
@@ -850,7 +799,7 @@ __device__ __forceinline__ void march(const RenderParams &P, float *L, int lane,
             }
             // (the flags these two leave are the tests below, taken on every lane at once)
             bool go = true, mine = true;
-            composite_group<K, 0, VR_ZERO_FILL>(P, R, go, 1.f, r, gg, b, alpha, thr);
+            composite_group<K, 0, true>(P, R, go, 1.f, r, gg, b, alpha, thr);
             advance_k<K>(P, mine, R.nsteps, R.t, R.tfar, R.pos, R.step, cap);  // to sample + K
           }
           // advance_k's exit test and the opacity exit (a ray that stopped at one sample of the group
@@ -886,7 +835,7 @@ __device__ __forceinline__ void march(const RenderParams &P, float *L, int lane,
           ++C.iter;
           C.lit += (MODE != 0 && __any(shaded)) ? 1u : 0u;
         }
-        composite_group<K, 0, VR_ZERO_FILL && !NANCHK && !SLAB>(P, R, R.alive, ex ? 1.f : 0.f, r, gg, b, alpha, thr);
+        composite_group<K, 0, !NANCHK && !SLAB>(P, R, R.alive, ex ? 1.f : 0.f, r, gg, b, alpha, thr);
         if (SLAB && !inside) {
           if (R.alive && group_any<K>(R.mine && !ex)) {  // left the slab still unfinished
             // the next slab resumes at the group's first sample beyond this one (samples of a
@@ -986,7 +935,7 @@ __device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t n, int run) {
 // both eyes.  Columns are counted on a virtual image of part_cols + pair_shift columns: the left
 // eye's pixel at virtual column xv, the right eye's at xv - pair_shift; every pixel of each eye
 // is marched once.  Unpartitioned frames only.
-// NL (round 6, VR_NL2): 2 / 1 -- a launch of exactly two lights (the metric frame, examples/example1.m)
+// NL (round 6): 2 / 1 -- a launch of exactly two lights (the metric frame, examples/example1.m)
 // or one (examples/example2.m, example3.m), whose tame march shades the lights it holds in registers
 // without a light loop (shade_fast NL); 0 -- any light count.
 template <int K, int MODE, bool AB_ALIAS, bool COUNT, bool SHARE2, bool BIG, int CAP, int SCHED, int NL>
@@ -1098,7 +1047,7 @@ __global__ __launch_bounds__(64 * VR_WG_WAVES, march_min_eu(CAP, SCHED)) void ma
   }
 }
 
-// Pre-leap launch (round 6, VR_PRELEAP; DESIGN.md s5 "Rays far apart in one wave"): a wave whose
+// Pre-leap launch (round 6; DESIGN.md s5 "Rays far apart in one wave"): a wave whose
 // live rays start more than VR_PRELEAP_SPREAD steps apart along their direction (a tile of rays
 // entering the volume through a face at a grazing angle: the columns next to the silhouette at
 // rotate(30,10,0) start 900-2700 samples apart) cannot probe one box for them all, so before the
@@ -1463,12 +1412,12 @@ static bool inject_bad_launch() {
 }
 
 // One march_kernel launch; a lit launch of one or two lights takes the NL = 1 / 2 kernel where the
-// lights are hoisted (march: VR_LIGHTS_HOIST's conditions).
+// lights are hoisted (march: the conditions of `pre`).
 template <int KK, int MODE, bool AB, bool CNT, bool SH, bool BG, int CAP, int SC>
 static void launch_one(const RenderParams &P, dim3 grid, dim3 blk, hipStream_t s) {
   // (on-the-fly gradient launches only: the lookup-gradient march, C3, measured 0.8 % slower with it,
   // 27.65-27.70 vs 27.44-27.47 ms, r6v)
-  constexpr bool NL2 = VR_NL2 && VR_LIGHTS_HOIST && MODE == 1 && KK > 1 && AB && SH && !BG && !CNT;
+  constexpr bool NL2 = MODE == 1 && KK > 1 && AB && SH && !BG && !CNT;
   const int nl = (NL2 && (P.num_lights == 2 || P.num_lights == 1)) ? P.num_lights : 0;
   if (NL2 && nl == 2) hipLaunchKernelGGL((march_kernel<KK, MODE, AB, CNT, SH, BG, CAP, SC, NL2 ? 2 : 0>), grid, blk, 0, s, P);
   else if (NL2 && nl == 1) hipLaunchKernelGGL((march_kernel<KK, MODE, AB, CNT, SH, BG, CAP, SC, NL2 ? 1 : 0>), grid, blk, 0, s, P);

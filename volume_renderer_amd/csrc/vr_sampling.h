@@ -247,13 +247,11 @@ __device__ __forceinline__ void fetch_small2(const DevTex &t, const AxF &ax, con
     v1 = lerp(lerp(c00, c10, ay1.w), lerp(c01, c11, ay1.w), az1.w);
   }
 }
-// The same lookups from the texture's z-paired copy (DevTex::zp, entries {v(i), v(i + pxy)}): a
-// 16-byte load at entry i holds the x-pair of plane z and of plane z + 1, so one lookup is two row
-// loads (rows y and y + 1) where fetch_small takes four, and touches half the cache lines.  The
-// lerps are fetch_small's, in its order, on the same values: bit-identical.
-#ifndef VR_LUT_ZPAIR
-#define VR_LUT_ZPAIR 1
-#endif
+// The same lookup from the texture's z-paired copy (DevTex::zp, entries {v(i), v(i + pxy)}), which the
+// host binds for a tame launch's LUT: a 16-byte load at entry i holds the x-pair of plane z and of
+// plane z + 1, so one lookup is two row loads (rows y and y + 1) where fetch_small takes four, and
+// touches half the cache lines.  The lerps are fetch_small's, in its order, on the same values:
+// bit-identical.
 __device__ __forceinline__ float lerp_zrows(const f4a8 &r0, const f4a8 &r1, const AxF &ax, const AxF &ay,
                                             const AxF &az) {
   const float c00 = lerp(r0.x, r0.z, ax.w), c10 = lerp(r1.x, r1.z, ax.w);
@@ -277,6 +275,7 @@ __device__ __forceinline__ float fetch_small_z(const RenderParams &P, const AxF 
   const f4a8 r1 = *reinterpret_cast<const f4a8 *>(b + (o2 + px8));
   return lerp_zrows(r0, r1, ax, ay, az);
 }
+// fetch_small2 from the z-paired copy: four row loads.
 __device__ __forceinline__ void fetch_small2_z(const RenderParams &P, const AxF &ax, const AxF &ay0, const AxF &az0,
                                                const AxF &ay1, const AxF &az1, float &v0, float &v1) {
   const float ox = fmaf(ax.fl, 8.f, P.lutz_fbase8);
@@ -308,10 +307,10 @@ __device__ __forceinline__ float lut_light(const DevTex &lut, const AxF &la, flo
 
 // Trilinear fetch of the three lookup-gradient textures at once from their interleaved copy
 // (RenderParams::gvec): eight aligned 16-byte corner loads, and each component goes through exactly
-// the interpolation fetch() applies to its own texture.  VR_GVEC_BRICK: padded voxel (X, Y, Z) is
-// entry ((Z/2 * by + Y/2) * bx + X/2) * 8 + (X&1) + 2 (Y&1) + 4 (Z&1) -- a cell's corners span
-// 1-8 lines (3.4 on average) where rows of the padded volume take 4-8 (4.5), and a wave's oblique
-// footprint touches fewer lines.  Without it: rows of the padded volume (pitches of `t`).
+// the interpolation fetch() applies to its own texture.  The copy is laid out in 2x2x2 bricks: padded
+// voxel (X, Y, Z) is entry ((Z/2 * by + Y/2) * bx + X/2) * 8 + (X&1) + 2 (Y&1) + 4 (Z&1) -- a cell's
+// corners span 1-8 lines (3.4 on average) where rows of the padded volume take 4-8 (4.5), and a wave's
+// oblique footprint touches fewer lines.
 // (Split into the eight corner loads and their interpolation; round 5 measured the loads issued
 // before the emission fetch slower -- C3 30.3-30.4 ms at 4 waves per SIMD, 34.8 at 5 with spills,
 // vs 28.8-29.0, r5w.)
@@ -319,27 +318,18 @@ struct GvCell {
   float4 a00, b00, a10, b10, a01, b01, a11, b11;
 };
 template <bool BIG>
-__device__ __forceinline__ GvCell gvec_load(const float *gvec, const DevTex &t, uint32_t row8, uint32_t plane8,
-                                            const Ax &ax, const Ax &ay, const Ax &az) {
+__device__ __forceinline__ GvCell gvec_load(const float *gvec, uint32_t row8, uint32_t plane8, const Ax &ax,
+                                            const Ax &ay, const Ax &az) {
   GvCell q;
-  if (VR_GVEC_BRICK) {
-    const uint32_t X = (uint32_t)(ax.i + 1), Y = (uint32_t)(ay.i + 1), Z = (uint32_t)(az.i + 1);
-    const uint32_t dx = (X & 1u) ? 7u : 1u, dy = (Y & 1u) ? row8 - 2u : 2u, dz = (Z & 1u) ? plane8 - 4u : 4u;
-    const uint32_t xy = ((X >> 1) << 3) + (X & 1u) + (Y >> 1) * row8 + ((Y & 1u) << 1) + ((Z & 1u) << 2);
-    uint64_t o;
-    if (BIG) o = (uint64_t)(Z >> 1) * plane8 + xy;
-    else o = (Z >> 1) * plane8 + xy;
-    const float4 *b = reinterpret_cast<const float4 *>(gvec) + o;
-    q.a00 = b[0], q.b00 = b[dx], q.a10 = b[dy], q.b10 = b[dy + dx];
-    q.a01 = b[dz], q.b01 = b[dz + dx], q.a11 = b[dz + dy], q.b11 = b[dz + dy + dx];
-  } else {
-    uint64_t o;
-    if (BIG) o = ((uint64_t)(az.i + 1) * t.pxy + (uint64_t)(ay.i + 1) * t.px) + (uint64_t)(ax.i + 1);
-    else o = ((uint32_t)(az.i + 1) * t.pxy + (uint32_t)(ay.i + 1) * t.px) + (uint32_t)(ax.i + 1);
-    const float4 *b = reinterpret_cast<const float4 *>(gvec) + o;
-    q.a00 = b[0], q.b00 = b[1], q.a10 = b[t.px], q.b10 = b[t.px + 1];
-    q.a01 = b[t.pxy], q.b01 = b[t.pxy + 1], q.a11 = b[t.pxy + t.px], q.b11 = b[t.pxy + t.px + 1];
-  }
+  const uint32_t X = (uint32_t)(ax.i + 1), Y = (uint32_t)(ay.i + 1), Z = (uint32_t)(az.i + 1);
+  const uint32_t dx = (X & 1u) ? 7u : 1u, dy = (Y & 1u) ? row8 - 2u : 2u, dz = (Z & 1u) ? plane8 - 4u : 4u;
+  const uint32_t xy = ((X >> 1) << 3) + (X & 1u) + (Y >> 1) * row8 + ((Y & 1u) << 1) + ((Z & 1u) << 2);
+  uint64_t o;
+  if (BIG) o = (uint64_t)(Z >> 1) * plane8 + xy;
+  else o = (Z >> 1) * plane8 + xy;
+  const float4 *b = reinterpret_cast<const float4 *>(gvec) + o;
+  q.a00 = b[0], q.b00 = b[dx], q.a10 = b[dy], q.b10 = b[dy + dx];
+  q.a01 = b[dz], q.b01 = b[dz + dx], q.a11 = b[dz + dy], q.b11 = b[dz + dy + dx];
   return q;
 }
 __device__ __forceinline__ f3 gvec_lerp(const GvCell &q, const Ax &ax, const Ax &ay, const Ax &az) {
@@ -358,9 +348,9 @@ __device__ __forceinline__ f3 gvec_lerp(const GvCell &q, const Ax &ax, const Ax 
   return r;
 }
 template <bool BIG>
-__device__ __forceinline__ f3 fetch_vec(const float *gvec, const DevTex &t, uint32_t row8, uint32_t plane8,
-                                        const Ax &ax, const Ax &ay, const Ax &az) {
-  return gvec_lerp(gvec_load<BIG>(gvec, t, row8, plane8, ax, ay, az), ax, ay, az);
+__device__ __forceinline__ f3 fetch_vec(const float *gvec, uint32_t row8, uint32_t plane8, const Ax &ax,
+                                        const Ax &ay, const Ax &az) {
+  return gvec_lerp(gvec_load<BIG>(gvec, row8, plane8, ax, ay, az), ax, ay, az);
 }
 
 // tex3D on any texture state (unbound -> 0, 1x1x1 -> single voxel through the same lerp algebra).
@@ -373,11 +363,6 @@ __device__ __forceinline__ float tex3d(const DevTex &t, float x, float y, float 
   }
   return fetch<BIG>(t, axis(x, t.nx, t.fnx), axis(y, t.ny, t.fny), axis(z, t.nz, t.fnz));
 }
-
-
-#ifndef VR_MIN_WAVES
-#define VR_MIN_WAVES 1
-#endif
 
 // Workgroup -> 16x16-pixel tile.  tile_mode 1 (XCD-aware): workgroups are dealt
 // round-robin to the 8 XCDs (b % 8 share one, observed -- a speed assumption only), so block b
@@ -443,21 +428,7 @@ __device__ __forceinline__ bool ray_setup(const RenderParams &P, int x, int y, f
 // a / b for the arguments of the angle acosf calls, bit-identical to IEEE a / b wherever it can
 // matter: the compiler's correctly rounded sequence (Newton-refined reciprocal, two residual
 // corrections) without its v_div_scale / v_div_fixup range handling, which is the identity for
-// 2^-40 <= |b| <= 2^40 and |a| <= 2^40 (tools/microbench: 2^33 random pairs, 0 mismatches).  Here
-// |a| <= |b| (Cauchy-Schwarz, up to rounding), and a tiny quotient gives acosf == pi/2 however it
-// rounds, so only b is tested; a wave with any other lane takes '/'.
-__device__ __forceinline__ float div_acos_arg(float a, float b) {
-  const uint32_t ub = __float_as_uint(b) & 0x7fffffffu;
-  if (__builtin_expect(__all(ub - 0x2b800000u <= 0x28000000u), 1)) {
-    const float y0 = __builtin_amdgcn_rcpf(b);
-    const float y1 = fmaf(fmaf(-b, y0, 1.f), y0, y0);
-    const float q0 = a * y1;
-    const float q1 = fmaf(fmaf(-b, q0, a), y1, q0);
-    return fmaf(fmaf(-b, q1, a), y1, q1);
-  }
-  return a / b;
-}
-
+// 2^-40 <= |b| <= 2^40 and |a| <= 2^40 (tools/microbench: 2^33 random pairs, 0 mismatches).
 __device__ __forceinline__ float div_fast(float a, float b) {
   const float y0 = __builtin_amdgcn_rcpf(b);
   const float y1 = fmaf(fmaf(-b, y0, 1.f), y0, y0);
@@ -465,14 +436,9 @@ __device__ __forceinline__ float div_fast(float a, float b) {
   const float q1 = fmaf(fmaf(-b, q0, a), y1, q0);
   return fmaf(fmaf(-b, q1, a), y1, q1);
 }
-// a / b with one residual correction on the hardware reciprocal (no Newton step on it): not always
-// correctly rounded (tools/microbench/cosine_check.hip counts how often it is not).
-__device__ __forceinline__ float div_short(float a, float b) {
-  const float y = __builtin_amdgcn_rcpf(b);
-  const float q0 = a * y;
-  return fmaf(fmaf(-b, q0, a), y, q0);
-}
-// div_acos_arg over a group with one wave-wide guard (see div_acos_arg for the exactness argument).
+// div_fast over a group with one wave-wide guard.  Here |a| <= |b| (Cauchy-Schwarz, up to rounding),
+// and a tiny quotient gives acosf == pi/2 however it rounds, so only b is tested; a wave with any
+// lane outside div_fast's range takes '/'.
 template <int N>
 __device__ __forceinline__ void div_acos_n(const float (&a)[N], const float (&b)[N], float (&q)[N]) {
   bool ok = true;
@@ -496,98 +462,10 @@ __device__ __forceinline__ float divpi(float x) {
   return fmaf(fmaf(-q, VR_PI, x), r, q);
 }
 
-// acos(q) / pi for the fast shading variant.  VR_FAST_ACOS 0: the device library's acospi (one
-// rounding, ~21 VALU); 1: acospi(t) = sqrt(1 - t) * P8(t) on t = |q| (the form of Abramowitz &
-// Stegun 4.4.46; P8 a weighted least-squares fit at Chebyshev nodes of acos(t) / (pi sqrt(1 - t)),
-// relative approximation error 2.4e-9), acospi(q) = 1 - acospi(-q) for q < 0: 13 VALU.  In fp32,
-// over every q in [-1, 1]: 94 % correctly rounded, at most 1.95 ulp.  NaN and |q| > 1 give NaN as
-// acosf does (sqrt of a negative).
-#ifndef VR_FAST_ACOS
-#define VR_FAST_ACOS 1
-#endif
-#ifndef VR_ACOS_LITERALS
-#define VR_ACOS_LITERALS 1
-#endif
-#ifndef VR_FAST_NLEN
-#define VR_FAST_NLEN 1  // 1: the fast variant takes the unit normal's length as 1 (shade_lights)
-#endif
-#ifndef VR_FAST_COS
-#define VR_FAST_COS 1  // 1: the fast variant's cosines as dot * rsq * rsq; 0: correctly rounded (ablation)
-#endif
-#ifndef VR_FAST_NX
-#define VR_FAST_NX 0  // 1: the fast variant's unit normal as the oracle's, -(g * (1 / sqrtf(g.g))), bit for bit
-#endif
-#ifndef VR_FAST_GX
-#define VR_FAST_GX 0  // 1: the fast variant's gamma cosines correctly rounded (the oracle's quotient)
-#endif
-#ifndef VR_FAST_NXQ
-#define VR_FAST_NXQ 0  // 1: the fast normal as -(g * v_rcp(v_sqrt(g.g))) (the oracle's op sequence, hardware ops)
-#endif
-#ifndef VR_FAST_GXQ
-#define VR_FAST_GXQ 0  // 1: gamma's cosine as dot / (v_sqrt(lip.lip) v_sqrt(lop.lop)), one-correction quotient
-#endif
-#ifndef VR_FAST_HYBQ
-// gamma's cosine as the oracle's correctly rounded quotient where |cos gamma| > VR_HYB_TG (parity
-// ablation, round 4): 2 per lane with the compiler's IEEE sequences, 1 per wave with the guarded
-// sequences, 0 never (default: VR_FAST_CLAMP takes care of what they fixed, at a fraction of their
-// +5 % cost).
-#define VR_FAST_HYBQ 0
-#endif
-#ifndef VR_FAST_HYBRID
-#define VR_FAST_HYBRID 0  // 1: rsq shading, and XN + XG shading where gamma is ill-conditioned (shade_fast)
-#endif
-#ifndef VR_HYB_TA
-#define VR_HYB_TA 0.01f  // hybrid: |lip|^2 < TA |li|^2 (view within asin(0.1) of the normal), same for lights
-#endif
-#ifndef VR_HYB_TG
-#define VR_HYB_TG 0.999f  // |cos gamma| > TG: the oracle's quotient (VR_FAST_HYBQ; below gamma = 0.0245 the
-                          // LUT taps clamp to one voxel and the weight no longer matters)
-#endif
-#ifndef VR_HYB_TU
-// ... and |cos gamma| < TU: beyond it gamma is within 0.0245 of 0 or pi, where both taps of the LUT's
-// gamma axis are the same voxel (the weight does not matter); 2: no upper bound
-#define VR_HYB_TU 2.f
-#endif
-#ifndef VR_RSQ_NR
-#define VR_RSQ_NR 0  // 1: one Newton step on every cosine's hardware rsq
-#endif
-// rsq of a cosine normalisation (VR_RSQ_NR: one Newton step y (1 + (1 - x y^2) / 2))
+// rsq of a cosine normalisation: the hardware reciprocal square root (1 ulp)
 __device__ __forceinline__ float rsq_c(float x) {
-  const float y = __builtin_amdgcn_rsqf(x);
-#if VR_RSQ_NR
-  const float r = fmaf(-(x * y), y, 1.f);
-  return fmaf(r * 0.5f, y, y);
-#else
-  return y;
-#endif
+  return __builtin_amdgcn_rsqf(x);
 }
-// RN(1 / RN(sqrt(x))), the oracle's 1.f / sqrtf(x), for x >= 0: the correctly rounded root and
-// the compiler's correctly rounded reciprocal sequence without its range fix-ups where every lane
-// of the wave has x = 0 or 2^-80 <= x <= 2^80 (the root then in [2^-40, 2^40], div_fast's identity
-// range); x = 0 gives +inf, as 1 / 0.  Other waves take the library operations.
-__device__ __forceinline__ float rcp_sqrt_cr(float x) {
-  const uint32_t u = __float_as_uint(x);
-  if (__builtin_expect(__all(u == 0u || u - 0x17800000u <= 0x50000000u), 1)) {
-    const float r = div_fast(1.f, sqrt_fast(x));
-    return u == 0u ? __builtin_inff() : r;
-  }
-  return 1.f / sqrtf(x);
-}
-extern "C" __device__ float __ocml_acospi_f32(float);
-__device__ __forceinline__ float acospi_q(float q);
-// acos(q) / pi of a fast-shading cosine (shade_fast).  VR_FAST_CLAMP (default 1, inside acospi_q at
-// no cost; 2: an explicit compare and select here): a cosine the rsq product rounds below -1 is
-// taken as -1, NaN kept.  Where the exact cosine lies within a few ulps
-// of -1 (a back-facing normal, a light opposite the view in the tangent plane) the rsq product and
-// the oracle's correctly rounded quotient round past -1 independently, and past it acosf is NaN,
-// which the LUT lookup reads as the coordinate 0 -- the LUT at angle 0 instead of pi.  The fp64
-// oracle never rounds past; taking the cosine as -1 agrees with it everywhere and with the fp32
-// oracle wherever that one does not round past either (where it does, the envelope |fp32 - fp64|
-// holds the difference).  Past +1 needs no care: angle 0 and the NaN's coordinate 0 read the same
-// LUT voxels.  This was the whole of the fast shading's remaining SURVEY 8c gap (DESIGN.md s6).
-#ifndef VR_FAST_CLAMP
-#define VR_FAST_CLAMP 1
-#endif
 // The leading coefficient of acospi_q's polynomial in a VGPR, for a caller that takes several angles
 // (shade_fast: one v_mov_b32 per shaded sample instead of one per angle).  `dep`, a value of the
 // sample, is an operand the move does not read: with it the compiler cannot hoist the constant out
@@ -597,28 +475,26 @@ __device__ __forceinline__ float acospi_c0(float dep) {
   asm("v_mov_b32 %0, 0x3967ab32" : "=v"(c) : "v"(dep));
   return c;
 }
-__device__ __forceinline__ float acospi_q(float q, float c0);
-__device__ __forceinline__ float acospi_f(float q, float c0) {
-  if (VR_FAST_CLAMP == 2) q = q < -1.f ? -1.f : q;  // (the explicit form: a compare and a select)
-  return acospi_q(q, c0);
-}
-__device__ __forceinline__ float acospi_q(float q) {
-#if VR_FAST_ACOS && VR_ACOS_LITERALS
-  float c0;
-  asm("v_mov_b32 %0, 0x3967ab32" : "=v"(c0));
-  return acospi_q(q, c0);
-#else
-  return acospi_q(q, 2.209365193e-04f);
-#endif
-}
+// acos(q) / pi of a fast-shading cosine (shade_fast): acospi(t) = sqrt(1 - t) * P8(t) on t = |q| (the
+// form of Abramowitz & Stegun 4.4.46; P8 a weighted least-squares fit at Chebyshev nodes of
+// acos(t) / (pi sqrt(1 - t)), relative approximation error 2.4e-9), acospi(q) = 1 - acospi(-q) for
+// q < 0: 13 VALU, where the device library's acospi takes ~21.  In fp32, over every q in [-1, 1]: 94 %
+// correctly rounded, at most 1.95 ulp.  NaN gives NaN, as acosf does.
+// A cosine the rsq product rounds past -1 is taken as -1 (at no cost: the sqrt's source modifier
+// below).  Where the exact cosine lies within a few ulps
+// of -1 (a back-facing normal, a light opposite the view in the tangent plane) the rsq product and
+// the oracle's correctly rounded quotient round past -1 independently, and past it acosf is NaN,
+// which the LUT lookup reads as the coordinate 0 -- the LUT at angle 0 instead of pi.  The fp64
+// oracle never rounds past; taking the cosine as -1 agrees with it everywhere and with the fp32
+// oracle wherever that one does not round past either (where it does, the envelope |fp32 - fp64|
+// holds the difference).  Past +1 needs no care: angle 0 and the NaN's coordinate 0 read the same
+// LUT voxels.  This was the whole of the fast shading's remaining SURVEY 8c gap (DESIGN.md s6).
 // c0: the polynomial's leading coefficient 0x3967ab32 (acospi_c0)
 __device__ __forceinline__ float acospi_q(float q, float c0) {
 #if VR_ABLATE & 2
   return fmaf(q, -0.5f, 0.5f);  // diagnostic: the angle's cost removed (wrong image)
 #endif
-#if VR_FAST_ACOS
   const float t = fabsf(q);
-#if VR_ACOS_LITERALS
   // the Horner steps as VOP2 v_fmaak_f32 with the coefficient as a literal: written as plain fmaf the
   // compiler folds |q| into VOP3 fmas, which take no literal on gfx950, and holds the eight
   // coefficients in SGPRs across the sample loop -- where they push other values into v_readlane
@@ -634,28 +510,14 @@ __device__ __forceinline__ float acospi_q(float q, float c0) {
       "v_fmaak_f32 %0, %0, %1, 0x3f000000"
       : "=&v"(p)
       : "v"(t), "v"(c0));
-#else
-  float p = c0;
-  p = fmaf(p, t, -1.277460018e-03f);
-  p = fmaf(p, t, 3.530717921e-03f);
-  p = fmaf(p, t, -6.615247577e-03f);
-  p = fmaf(p, t, 1.037604921e-02f);
-  p = fmaf(p, t, -1.610660180e-02f);
-  p = fmaf(p, t, 2.833945118e-02f);
-  p = fmaf(p, t, -6.830968708e-02f);
-  p = fmaf(p, t, 0.5f);
-#endif
-  // VR_FAST_CLAMP 1: sqrt(|1 - t|) -- a free source modifier -- is the clamp of acospi_f for the few
-  // ulps a rounded cosine can exceed 1 in magnitude (the result within sqrt(ulp) of 0 or 1, in the
-  // LUT's clamped end cell either way) and keeps NaN; with 1 - t alone they are NaN (coordinate 0)
-  const float r = __builtin_amdgcn_sqrtf(VR_FAST_CLAMP == 1 ? fabsf(1.f - t) : 1.f - t) * p;
+  // sqrt(|1 - t|) -- a free source modifier -- is the clamp for the few ulps a rounded cosine can
+  // exceed 1 in magnitude (the result within sqrt(ulp) of 0 or 1, in the LUT's clamped end cell either
+  // way) and keeps NaN; with 1 - t alone they would be NaN (coordinate 0)
+  const float r = __builtin_amdgcn_sqrtf(fabsf(1.f - t)) * p;
   // q < 0 ? 1 - r : r without a compare: fma(-1, r, 1) rounds as 1 - r, fma(1, r, 0) is r (q = -0
   // takes the first form: 1 - 0.5 = 0.5 = r, the same value)
   const float sg = __builtin_copysignf(1.f, q);
   return fmaf(sg, r, fmaf(-0.5f, sg, 0.5f));
-#else
-  return __ocml_acospi_f32(q);
-#endif
 }
 
 // exp(-x) rounded to nearest, as the oracle's expf (glibc, < 0.502 ulp) gives it: for |x| < 2^-7
@@ -726,80 +588,42 @@ __device__ __forceinline__ float voxel0(const float *p) {
   return ((cptr)p)[0];
 }
 
-// The fast variant's shading (shade_lights FAST).  XN: the unit normal bit for bit as the oracle's
-// (the correctly rounded 1 / sqrtf); XG: gamma's cosine as the oracle's correctly rounded quotient.
-// NEED: set `need` where the sample's gamma is ill-conditioned -- the view or a light direction
-// within asin(sqrt(VR_HYB_TA)) of the normal (its projection onto the tangent plane cancels, so the
-// normal's last bits decide its direction) or a gamma cosine beyond +-VR_HYB_TG (acos amplifies the
-// cosine's rounding there) -- where the hybrid shading (VR_FAST_HYBRID) takes XN + XG.
+// The fast variant's shading (shade_lights FAST).
 // NL (round 6): the launch's light count when the kernel was specialised on it (2: the metric frame
 // and examples/example1.m; 1: examples/example2.m and example3.m -- the lights are the caller's
 // hoisted `pre`, no light loop, no masks of the loop bounds held across the sample loop); 0:
 // P.num_lights.
-template <bool TAME, bool XN, bool XG, bool NEED, int NL = 0>
+template <bool TAME, int NL = 0>
 __device__ __forceinline__ void shade_fast(const RenderParams &P, const f3 g, const f3 pos, const f3 o,
-                                          const float refl, float &ir, float &ig, float &ib, bool &need,
+                                          const float refl, float &ir, float &ig, float &ib,
                                           const DevLight *pre = nullptr) {
   static_assert(NL == 0 || ((NL == 1 || NL == 2) && TAME), "specialised for hoisted lights only");
   const int nl = NL ? NL : P.num_lights;
   // the sample's angles (1 + 2 per light) share the polynomial's leading coefficient: one move here
-#if VR_FAST_ACOS && VR_ACOS_LITERALS
   const float c0 = acospi_c0(g.x);
-#else
-  const float c0 = 2.209365193e-04f;
-#endif
-  auto ang = [&](float q) { return acospi_f(q, c0); };
+  auto ang = [&](float q) { return acospi_q(q, c0); };
   // n = -g * rsq(g.g): rsq(0) = inf gives the reference's NaN normal for a zero gradient
-  float ginv;
-  if constexpr (XN) ginv = rcp_sqrt_cr(dot3(g, g));  // the oracle's 1 / sqrtf(g.g), bit for bit
-  else if (VR_FAST_NXQ) ginv = __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(dot3(g, g)));
-  else ginv = __builtin_amdgcn_rsqf(dot3(g, g));
+  const float ginv = __builtin_amdgcn_rsqf(dot3(g, g));
   const f3 n = mk(-(g.x * ginv), -(g.y * ginv), -(g.z * ginv));
   const f3 li = mk(o.x - pos.x, o.y - pos.y, o.z - pos.z);
   const float dli = dot3(li, n);
   const f3 lip = mk(fmaf(-dli, n.x, li.x), fmaf(-dli, n.y, li.y), fmaf(-dli, n.z, li.z));
-  // |n| is 1 to within the rsq's ulp: its length is not divided out again (VR_FAST_NLEN 0 does)
-#if VR_FAST_NLEN
-  const float rn = 1.f;
-#else
-  const float rn = rsq_c(dot3(n, n));
-#endif
-  // XG: gamma's cosine as the oracle's dot(lip, lop) / (|lip| |lop|): `rlip` then holds |lip|
+  // (|n| is 1 to within the rsq's ulp: its length is not divided out of the cosines again)
   const float lip2 = dot3(lip, lip), li2 = dot3(li, li);
-  const float rlip = XG ? sqrt_cr(lip2) : (VR_FAST_GXQ ? __builtin_amdgcn_sqrtf(lip2) : rsq_c(lip2));
-  // the cosine of gamma for light vector lo (its projection lop); NEED: the sample is in a region
-  // where gamma is ill-conditioned (see shade_lights)
-  auto gamma_q = [&](const f3 &lo, const f3 &lop) {
+  const float rlip = rsq_c(lip2);
+  // the cosine of gamma for a light vector's projection lop
+  auto gamma_q = [&](const f3 &lop) {
     const float lop2 = dot3(lop, lop);
-    float q;
-    if constexpr (XG) q = div_acos_arg(dot3(lip, lop), rlip * sqrt_cr(lop2));
-    else if (VR_FAST_GXQ) q = div_short(dot3(lip, lop), rlip * __builtin_amdgcn_sqrtf(lop2));
-    else q = dot3(lip, lop) * (rlip * rsq_c(lop2));
-    if constexpr (NEED) need = need || fabsf(q) > VR_HYB_TG || lop2 < VR_HYB_TA * dot3(lo, lo);
-    if constexpr (VR_FAST_HYBQ == 2 && !XG && !NEED) {
-      // per lane, no wave-wide guard: near |cos| = 1 (where acos amplifies the cosine's rounding) the
-      // oracle's quotient dot / (sqrtf(lip.lip) sqrtf(lop.lop)) with the compiler's IEEE sequences
-      const float aq = fabsf(q);
-      if (__builtin_expect(aq > VR_HYB_TG && aq < VR_HYB_TU, 0)) q = dot3(lip, lop) / (sqrtf(lip2) * sqrtf(lop2));
-    } else if constexpr (VR_FAST_HYBQ == 1 && !XG && !NEED) {
-      // near |cos| = 1 acos amplifies the cosine's rounding: there the oracle's quotient
-      const bool nd = fabsf(q) > VR_HYB_TG;
-      if (__builtin_expect(__any(nd), 0)) {
-        const float qx = div_acos_arg(dot3(lip, lop), sqrt_cr(lip2) * sqrt_cr(lop2));
-        if (nd) q = qx;
-      }
-    }
-    return q;
+    return dot3(lip, lop) * (rlip * rsq_c(lop2));
   };
-  if constexpr (NEED) need = lip2 < VR_HYB_TA * li2;
-  const float alpha_n = ang(dot3(n, li) * (rn * rsq_c(li2)));
+  const float alpha_n = ang(dot3(n, li) * rsq_c(li2));
   const AxF la = axis_lut<true, TAME>(alpha_n, P.lut.fnx);
   int i = 0;
   if (TAME || (P.lut.p != nullptr && P.lut.small && !P.lut.one)) {
     // the common LUT (bound, below 2^22 padded voxels): one wave-uniform test for the frame's
-    // lights; a pair's eight LUT row loads are issued together, ahead of their lerps
+    // lights; a pair's LUT row loads are issued together, ahead of their lerps
     for (; i + 1 < nl; i += 2) {
-      // pre: the first pair held in registers by the caller (vr_march.hip VR_LIGHTS_HOIST)
+      // pre: the first pair held in registers by the caller (vr_march.hip march)
       const DevLight L0 = NL == 2 ? pre[0] : ((pre && i == 0) ? pre[0] : light_at(P, i));
       const DevLight L1 = NL == 2 ? pre[1] : ((pre && i == 0) ? pre[1] : light_at(P, i + 1));
       const f3 lo0 = mk(L0.px - pos.x, L0.py - pos.y, L0.pz - pos.z);
@@ -807,16 +631,16 @@ __device__ __forceinline__ void shade_fast(const RenderParams &P, const f3 g, co
       const float dlo0 = dot3(lo0, n), dlo1 = dot3(lo1, n);
       const f3 lop0 = mk(fmaf(-dlo0, n.x, lo0.x), fmaf(-dlo0, n.y, lo0.y), fmaf(-dlo0, n.z, lo0.z));
       const f3 lop1 = mk(fmaf(-dlo1, n.x, lo1.x), fmaf(-dlo1, n.y, lo1.y), fmaf(-dlo1, n.z, lo1.z));
-      const float beta0 = ang(dlo0 * (rn * rsq_c(dot3(lo0, lo0))));
-      const float gamma0 = ang(gamma_q(lo0, lop0));
-      const float beta1 = ang(dlo1 * (rn * rsq_c(dot3(lo1, lo1))));
-      const float gamma1 = ang(gamma_q(lo1, lop1));
+      const float beta0 = ang(dlo0 * rsq_c(dot3(lo0, lo0)));
+      const float gamma0 = ang(gamma_q(lop0));
+      const float beta1 = ang(dlo1 * rsq_c(dot3(lo1, lo1)));
+      const float gamma1 = ang(gamma_q(lop1));
       float light0, light1;
 #if VR_ABLATE & 1  // diagnostic: the LUT fetch's cost removed (wrong image)
       light0 = beta0 + gamma0 + la.w;
       light1 = beta1 + gamma1 + la.w;
 #else
-      if (TAME && VR_LUT_ZPAIR)  // the host binds a tame launch's LUT with its z-paired copy
+      if (TAME)  // the host binds a tame launch's LUT with its z-paired copy
         fetch_small2_z(P, la, axis_lut<true, TAME>(beta0, P.lut.fny), axis_lut<true, TAME>(gamma0, P.lut.fnz),
                        axis_lut<true, TAME>(beta1, P.lut.fny), axis_lut<true, TAME>(gamma1, P.lut.fnz), light0, light1);
       else
@@ -840,10 +664,10 @@ __device__ __forceinline__ void shade_fast(const RenderParams &P, const f3 g, co
     const float dlo0 = dot3(lo0, n), dlo1 = dot3(lo1, n);
     const f3 lop0 = mk(fmaf(-dlo0, n.x, lo0.x), fmaf(-dlo0, n.y, lo0.y), fmaf(-dlo0, n.z, lo0.z));
     const f3 lop1 = mk(fmaf(-dlo1, n.x, lo1.x), fmaf(-dlo1, n.y, lo1.y), fmaf(-dlo1, n.z, lo1.z));
-    const float beta0 = ang(dlo0 * (rn * rsq_c(dot3(lo0, lo0))));
-    const float gamma0 = ang(gamma_q(lo0, lop0));
-    const float beta1 = ang(dlo1 * (rn * rsq_c(dot3(lo1, lo1))));
-    const float gamma1 = ang(gamma_q(lo1, lop1));
+    const float beta0 = ang(dlo0 * rsq_c(dot3(lo0, lo0)));
+    const float gamma0 = ang(gamma_q(lop0));
+    const float beta1 = ang(dlo1 * rsq_c(dot3(lo1, lo1)));
+    const float gamma1 = ang(gamma_q(lop1));
     const float light0 = lut_light<true>(P.lut, la, beta0, gamma0);
     const float light1 = lut_light<true>(P.lut, la, beta1, gamma1);
     const float rl0 = refl * light0;
@@ -860,12 +684,10 @@ __device__ __forceinline__ void shade_fast(const RenderParams &P, const f3 g, co
     const f3 lo = mk(L.px - pos.x, L.py - pos.y, L.pz - pos.z);
     const float dlo = dot3(lo, n);
     const f3 lop = mk(fmaf(-dlo, n.x, lo.x), fmaf(-dlo, n.y, lo.y), fmaf(-dlo, n.z, lo.z));
-    const float beta = ang(dlo * (rn * rsq_c(dot3(lo, lo))));
-    const float gamma = ang(gamma_q(lo, lop));
-    const float rl = refl * (TAME ? (VR_LUT_ZPAIR ? fetch_small_z(P, la, axis_lut<true, TAME>(beta, P.lut.fny),
-                                                                 axis_lut<true, TAME>(gamma, P.lut.fnz))
-                                                  : fetch_small(P.lut, la, axis_lut<true, TAME>(beta, P.lut.fny),
-                                                                axis_lut<true, TAME>(gamma, P.lut.fnz)))
+    const float beta = ang(dlo * rsq_c(dot3(lo, lo)));
+    const float gamma = ang(gamma_q(lop));
+    const float rl = refl * (TAME ? fetch_small_z(P, la, axis_lut<true, TAME>(beta, P.lut.fny),
+                                                  axis_lut<true, TAME>(gamma, P.lut.fnz))
                                   : lut_light<true>(P.lut, la, beta, gamma));
     ir = fmaf(rl * L.cr, P.color[0], ir);
     ig = fmaf(rl * L.cg, P.color[1], ig);
@@ -877,66 +699,8 @@ template <bool FAST, bool TAME = false, int NL = 0>
 __device__ __forceinline__ void shade_lights(const RenderParams &P, const f3 g, const f3 pos, const f3 o,
                                              const float refl, float &ir, float &ig, float &ib,
                                              const DevLight *pre = nullptr) {
-#if !VR_FAST_COS
   if constexpr (FAST) {
-    // VR_FAST_COS 0 (parity ablation): the normal and the angle cosines in the exact variant's
-    // correctly rounded op sequence (the oracle's), only acos/pi as acospi_q and the opacity as
-    // exp2 differ from it
-    const float ginv = 1.f / sqrt_cr(dot3(g, g));
-    const f3 n = mk(-(g.x * ginv), -(g.y * ginv), -(g.z * ginv));
-    const f3 li = mk(o.x - pos.x, o.y - pos.y, o.z - pos.z);
-    const float dli = dot3(li, n);
-    const f3 lip = mk(fmaf(-dli, n.x, li.x), fmaf(-dli, n.y, li.y), fmaf(-dli, n.z, li.z));
-    float sq_in[3] = {dot3(n, n), dot3(li, li), dot3(lip, lip)}, sq[3];
-    sqrt_cr_n<3>(sq_in, sq);
-    const float nlen = sq[0], liplen = sq[2];
-    float alpha_n;
-    {
-      const float num[1] = {dot3(n, li)}, den[1] = {nlen * sq[1]};
-      float q[1];
-      div_acos_n<1>(num, den, q);
-      alpha_n = acospi_q(q[0]);
-    }
-    const AxF la = axis_lut<true>(alpha_n, P.lut.fnx);
-    for (int i = 0; i < P.num_lights; ++i) {
-      const DevLight L = light_at(P, i);
-      const f3 lo = mk(L.px - pos.x, L.py - pos.y, L.pz - pos.z);
-      const float dlo = dot3(lo, n);
-      const f3 lop = mk(fmaf(-dlo, n.x, lo.x), fmaf(-dlo, n.y, lo.y), fmaf(-dlo, n.z, lo.z));
-      float li_in[2] = {dot3(lo, lo), dot3(lop, lop)}, ln[2];
-      sqrt_cr_n<2>(li_in, ln);
-      const float num[2] = {dot3(n, lo), dot3(lip, lop)}, den[2] = {nlen * ln[0], liplen * ln[1]};
-      float q[2];
-      div_acos_n<2>(num, den, q);
-      const float rl = refl * lut_light<true>(P.lut, la, acospi_q(q[0]), acospi_q(q[1]));
-      ir = fmaf(rl * L.cr, P.color[0], ir);
-      ig = fmaf(rl * L.cg, P.color[1], ig);
-      ib = fmaf(rl * L.cb, P.color[2], ib);
-    }
-  } else
-#endif
-  if constexpr (FAST) {
-#if VR_FAST_HYBRID
-    // the rsq-based shading everywhere, and where gamma is ill-conditioned (NEED) the sample's
-    // shading again with the oracle's normal and gamma cosines (per lane: the image does not depend
-    // on which lanes share a wave)
-    bool need = false;
-    const float ir0 = ir, ig0 = ig, ib0 = ib;
-    shade_fast<TAME, false, false, true>(P, g, pos, o, refl, ir, ig, ib, need);
-    if (__any(need)) {
-      float er = ir0, eg = ig0, eb = ib0;
-      bool unused = false;
-      shade_fast<TAME, true, true, false>(P, g, pos, o, refl, er, eg, eb, unused);
-      if (need) {
-        ir = er;
-        ig = eg;
-        ib = eb;
-      }
-    }
-#else
-    bool unused = false;
-    shade_fast<TAME, VR_FAST_NX, VR_FAST_GX, false, NL>(P, g, pos, o, refl, ir, ig, ib, unused, pre);
-#endif
+    shade_fast<TAME, NL>(P, g, pos, o, refl, ir, ig, ib, pre);
   } else {
     // surface normal n = -normalize(g); normalize(0) = 0 * inf = NaN as in the reference.
     // Correctly rounded 1/sqrtf, bit-identical to the oracle: the projections li - (li.n)n below

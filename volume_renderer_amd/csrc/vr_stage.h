@@ -44,9 +44,6 @@ static __constant__ const UdivTab udiv_tab = make_udiv_tab();
 #ifndef VR_STAGE_UNROLL
 #define VR_STAGE_UNROLL 4  // loads in flight per lane while staging
 #endif
-#ifndef VR_STAGE_NT
-#define VR_STAGE_NT 0  // 1 (A/B): staging loads with the non-temporal hint (L2 streaming policy)
-#endif
 #ifndef VR_CHUNK
 #define VR_CHUNK 32      // samples per staged chunk (halved while the box does not fit)
 #endif
@@ -86,7 +83,7 @@ __device__ __forceinline__ int wave_min(int v) { return wave_reduce<false>(v); }
 __device__ __forceinline__ int wave_max(int v) { return wave_reduce<true>(v); }
 
 // wave_reduce<false> of two int16 fields packed in one dword, component-wise (v_pk_min_i16): the
-// chunk box's six bounds in three reductions (plan_chunk, VR_PACKED_BOUNDS).
+// chunk box's six bounds in three reductions (plan_chunk).
 typedef short vr_s2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ int pk_min(int a, int b) {
   return __builtin_bit_cast(int, __builtin_elementwise_min(__builtin_bit_cast(vr_s2, a), __builtin_bit_cast(vr_s2, b)));
@@ -138,22 +135,9 @@ __device__ __forceinline__ void wave_min2x3(int a, int b, int c, int &ra, int &r
 __device__ __forceinline__ int pk2(int lo16, int hi16) { return (lo16 & 0xffff) | (int)((uint32_t)hi16 << 16); }
 __device__ __forceinline__ int pk_lo(int v) { return (int)(short)(v & 0xffff); }
 __device__ __forceinline__ int pk_hi(int v) { return v >> 16; }
-#ifndef VR_PACKED_BOUNDS
-#define VR_PACKED_BOUNDS 1
-#endif
-
-#ifndef VR_RELOAD_TEX
-#define VR_RELOAD_TEX 0
-#endif
-
-#ifndef VR_ODD_PITCH
-// LDS row / plane pitches: 0 dense (ex, ex * ey); 1 always odd (measured slower: the larger slots
-// overflow more); 2 odd when the padded box still fits the slot, dense otherwise
-#define VR_ODD_PITCH 0
-#endif
 
 // Staged box: padded-volume index ranges [r0, r0 + e) per axis, stored in the slot with row
-// pitch px and plane pitch pxy (odd, so that rows and planes start on rotating banks).
+// pitch px and plane pitch pxy (dense: ex and ex * ey).
 struct Box {
   int rx, ry, rz, ex, ey, ez, px, pxy;
 };
@@ -267,32 +251,6 @@ __device__ __forceinline__ bool in_box(int l, int e) {
   return (VR_ABLATE & 16) || (unsigned)l < (unsigned)(e - 1);
 }
 
-// A texture's parameters re-read from the kernel-argument segment at the point of use (scalar loads)
-// for the rare global-memory taps: behind the empty asm the compiler cannot hoist the loads out of
-// the sample loop, so they do not hold SGPRs across it (the loop's SGPRs spill to VGPR lanes
-// otherwise, and every spilled value costs a v_readlane per use).
-__device__ __forceinline__ DevTex reload(const DevTex &t) {
-#if VR_RELOAD_TEX == 1
-  typedef const volatile __attribute__((address_space(4))) DevTex *cptr;
-  cptr q = (cptr)&t;
-  DevTex u;
-  u.p = q->p;
-  u.nx = q->nx;
-  u.ny = q->ny;
-  u.nz = q->nz;
-  u.px = q->px;
-  u.pxy = q->pxy;
-  return u;
-#elif VR_RELOAD_TEX == 2
-  typedef const __attribute__((address_space(4))) DevTex *cptr;
-  cptr q = (cptr)&t;
-  asm volatile("" : "+s"(q));
-  return *q;
-#else
-  return t;
-#endif
-}
-
 // Trilinear fetch of the staged emission texture: the slot when the 2x2x2 cell lies in the box
 // (`in`, with slot word `a`), global memory otherwise -- the same interpolation either way.  The
 // axes are unclamped (axis_raw); the global path clamps them.
@@ -300,7 +258,7 @@ template <bool BIG>
 __device__ __forceinline__ float fetch_at(const DevTex &t, const float *L, const Box &B, bool in, int a,
                                           const Ax &ax, const Ax &ay, const Ax &az) {
   if (in) return lds_tri(L, B, a, ax.w, ay.w, az.w);
-  const DevTex u = reload(t);
+  const DevTex u = t;  // (a copy: read in place, a few kernels' registers are allocated differently)
   return fetch<BIG>(u, clamp_ax(ax, u.nx), clamp_ax(ay, u.ny), clamp_ax(az, u.nz));
 }
 
@@ -359,48 +317,6 @@ __device__ __forceinline__ bool stage_box_elems(float *L, const DevTex &t, const
   return __any(nz);
 }
 
-
-#ifndef VR_STAGE_GLDS
-#define VR_STAGE_GLDS 0  // (A/B) stage dense boxes with LDS-DMA loads (global_load_lds_dword)
-#endif
-
-// Copy a densely pitched box B into the slot with LDS-DMA loads: a dense slot is the box's V voxels
-// in x-fastest order, so slot words q0 .. q0 + 63 of one wave pass are the lane-linear destination
-// of one global_load_lds_dword (LDS address = slot + 4 q0 + 4 lane); no VGPR holds a voxel and no
-// ds_write is issued.  The non-zero test reads the slot back (one word per lane per pass).
-template <bool BIG>
-__device__ __forceinline__ bool stage_box_glds(float *L, const DevTex &t, const Box &B, int lane) {
-  const uint32_t ex = (uint32_t)B.ex, ey = (uint32_t)B.ey;
-  const uint32_t V = ex * ey * (uint32_t)B.ez;
-  uint32_t x = (uint32_t)lane % ex, r = (uint32_t)lane / ex;
-  uint32_t y = r % ey;
-  const float *src = t.p + ((uint64_t)(B.rz + r / ey) * t.pxy + (uint64_t)(B.ry + y) * t.px + (uint64_t)(B.rx + x));
-  const uint32_t sx = 64u % ex, sr = 64u / ex;
-  const int64_t g_step = (int64_t)sx + (int64_t)sr * (int64_t)t.px;
-  const int64_t g_row = (int64_t)t.px - (int64_t)ex, g_wrap = (int64_t)t.pxy - (int64_t)ey * (int64_t)t.px;
-  __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the previous chunk's slot reads are done
-  for (uint32_t q0 = 0; q0 < V; q0 += 64u) {
-    if (q0 + (uint32_t)lane < V)
-      __builtin_amdgcn_global_load_lds((const void *)src, (__attribute__((address_space(3))) void *)(L + q0), 4, 0, 0);
-    x += sx;
-    y += sr;
-    src += g_step;
-    if (x >= ex) {
-      x -= ex;
-      ++y;
-      src += g_row;
-    }
-    while (y >= ey) {
-      y -= ey;
-      src += g_wrap;
-    }
-  }
-  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the slot is written
-  uint32_t acc = 0;
-  for (uint32_t q = (uint32_t)lane; q < V; q += 64u) acc |= __float_as_uint(L[q]);
-  return __any((acc & 0x7fffffffu) != 0u);
-}
-
 // Copy box B of the apron volume into the wave's LDS slot (row-major, x fastest).  A wave pass
 // moves 64 / ex whole rows (lane -> (row slot, x)); row offsets advance incrementally, relative to
 // a wave-uniform base pointer, so a pass costs a handful of adds instead of per-element 64-bit
@@ -409,9 +325,6 @@ __device__ __forceinline__ bool stage_box_glds(float *L, const DevTex &t, const 
 template <bool BIG>
 __device__ __forceinline__ bool stage_box(float *L, const DevTex &t, const Box &B, int lane) {
   const int ex = B.ex, ey = B.ey;
-  if (VR_STAGE_GLDS && B.px == ex && B.pxy == ex * ey &&
-      (BIG || (uint64_t)t.pxy * (uint64_t)B.ez * 4u < 0xFFFFFFFFull))
-    return stage_box_glds<BIG>(L, t, B, lane);
   const int rows = ey * B.ez;
   // (32-bit byte offsets overflow; rows: the bound of udiv_small's dividend below, which no slot's box
   // reaches)
@@ -457,7 +370,7 @@ __device__ __forceinline__ bool stage_box(float *L, const DevTex &t, const Box &
       li[j] = l;
       if (k0 + j < n) {
         const float *src = reinterpret_cast<const float *>(base + g);
-        v[j] = VR_STAGE_NT ? __builtin_nontemporal_load(src) : *src;
+        v[j] = *src;
       }
       l += l_row;
       g += g_row;
@@ -479,10 +392,6 @@ __device__ __forceinline__ bool stage_box(float *L, const DevTex &t, const Box &
   return __any((acc & 0x7fffffffu) != 0u);  // (the sign bit masked once, after the OR: -0 is empty)
 }
 
-#ifndef VR_PARTIAL
-#define VR_PARTIAL 1     // stage a centred sub-box when no whole box fits (taps outside: global)
-#endif
-
 // Chunk set-up: the box of every tap the wave's live rays take in their next S samples, S halved
 // (up to VR_ATTEMPTS tries) until the box fits the slot.  When none fits, the last box is shrunk
 // about its centre until it does (partial = true): taps outside it read global memory (the
@@ -497,7 +406,7 @@ __device__ __forceinline__ void plan_chunk(const RenderParams &P, bool alive, co
   const f3 bmin = mk(P.bmin[0], P.bmin[1], P.bmin[2]);
   const f3 bsc = mk(P.bscale[0], P.bscale[1], P.bscale[2]);
   const float tstep = P.tstep;
-  S = s0;  // the first attempt (VR_CHUNK, or the wave's guess from its last chunk: VR_ADAPTIVE_S)
+  S = s0;  // the first attempt (VR_CHUNK, or the wave's guess from its last chunk: vr_march.hip march)
   staged = false;
   partial = false;
   B = Box{0, 0, 0, 1, 1, 1, 1, 1};
@@ -516,7 +425,7 @@ __device__ __forceinline__ void plan_chunk(const RenderParams &P, bool alive, co
       axis_range(((pos.z - bmin.z) * bsc.z) * E.fnz - 0.5f, ((pe.z - bmin.z) * bsc.z) * E.fnz - 0.5f,
                  P.tap_off[2], E.nz, lo[2], hi[2], edge);
     }
-    if (VR_PACKED_BOUNDS && E.nx < 16000 && E.ny < 16000 && E.nz < 16000) {
+    if (E.nx < 16000 && E.ny < 16000 && E.nz < 16000) {
       // padded bounds lie in [0, n + 1] (and the dead-lane sentinels are clamped to +-16383), so
       // they fit int16 fields: lo x/y, lo z / -hi x, -hi y / -hi z, each pair in one reduction
       const int c = 16383;
@@ -537,18 +446,11 @@ __device__ __forceinline__ void plan_chunk(const RenderParams &P, bool alive, co
       B.ey = wave_max(hi[1]) - B.ry + 1;
       B.ez = wave_max(hi[2]) - B.rz + 1;
     }
-    B.px = VR_ODD_PITCH == 1 ? (B.ex | 1) : B.ex;
-    B.pxy = VR_ODD_PITCH == 1 ? ((B.px * B.ey) | 1) : B.px * B.ey;
+    B.px = B.ex;
+    B.pxy = B.px * B.ey;
     if (vol_out) *vol_out = B.pxy * B.ez;
     if (B.ex <= 0 || B.ey <= 0 || B.ez <= 0) return;  // no live ray
     if (B.pxy * B.ez <= CAP) {
-      if (VR_ODD_PITCH == 2) {  // rows and planes on rotating banks, if the slot has room
-        const int px = B.ex | 1, pxy = (px * B.ey) | 1;
-        if (pxy * B.ez <= CAP) {
-          B.px = px;
-          B.pxy = pxy;
-        }
-      }
       staged = true;
       if (edge_out) *edge_out = __any(edge);
       return;
@@ -556,7 +458,6 @@ __device__ __forceinline__ void plan_chunk(const RenderParams &P, bool alive, co
     if (S <= (VR_CHUNK >> (VR_ATTEMPTS - 1))) break;  // the shortest chunk did not fit either
     S >>= 1;
   }
-#if VR_PARTIAL
   // shrink the largest extent about the centre until the sub-box fits (wave-uniform scalars)
   int e[3] = {B.ex, B.ey, B.ez}, r[3] = {B.rx, B.ry, B.rz};
   while (e[0] * e[1] * e[2] > CAP) {
@@ -574,7 +475,6 @@ __device__ __forceinline__ void plan_chunk(const RenderParams &P, bool alive, co
     partial = true;
     return;
   }
-#endif
   S >>= 1;  // no box fits: march S/2 samples from global memory
 }
 
@@ -688,39 +588,25 @@ __device__ __forceinline__ int box_bricks_empty(KParams kp0, int rx, int ry, int
   return __any(v != 0u) ? 0 : 1;
 }
 
-// Per-lane empty-space probe (round 6): whether every centre tap of each live lane's own next L
-// samples lies in +-0 bricks -- the test for waves whose rays are too far apart for one box
-// (probe_run's -1).  Rays that graze a volume face enter it at very different depths (a column of
-// pixels whose rays run almost parallel to the face: rotate(30,10,0) at 1920x1080, the 8 columns
-// next to the silhouette), so a wave's live rays spread along the face, its probe box spans
-// hundreds of bricks and its chunk boxes stage only partially: before round 6 such a block marched
-// its ~7000 empty samples per ray with global gathers, up to 55 ms.  Here each lane walks its own
-// run in segments of at most VR_LANE_SEG texels per axis; a segment's box (its end points' cells
-// widened by probe_off, as probe_run's box) spans at most 2 bricks per axis, whose bytes are ORed.
-// Consecutive segments share their end points bit for bit (both from the same expression), so the
-// segments cover the run's box end to end.  Returns 1 (all empty: leap) or 0.  Wave-uniform.
-#ifndef VR_LANE_SEG
-#define VR_LANE_SEG 4.0f
-#endif
-// The walk of one lane (no wave operations inside, every launch constant an argument).  Inlined it
-// weighs on the sample loop of every launch although it rarely runs (round 6, same box: metric frame
-// 25.34-25.40 vs 24.89-25.00 ms without the lane probe, C3 28.8-28.9 vs 27.5-27.7); out of line
-// (VR_PROBE_LANES_CALL=1) the call's register saves spill more (metric kernel 5 VGPRs), so inline.
-#ifndef VR_PROBE_LANES_CALL
-#define VR_PROBE_LANES_CALL 0
-#endif
-#if VR_PROBE_LANES_CALL
-#define VR_LANES_ATTR __attribute__((noinline))
-#else
-#define VR_LANES_ATTR __forceinline__
-#endif
-__device__ VR_LANES_ATTR uint32_t probe_lane_walk(const uint8_t *occ, uint32_t obx, uint32_t obxy, float a0x, float a0y,
+// Per-lane walk of the occupancy map (round 6, vr_march.hip preleap_kernel): whether every centre tap
+// of one lane's own run, from a0 to a1 in texel coordinates, lies in +-0 bricks -- the test for waves
+// whose rays are too far apart for one box (probe_run's -1).  Rays that graze a volume face enter it
+// at very different depths (a column of pixels whose rays run almost parallel to the face:
+// rotate(30,10,0) at 1920x1080, the 8 columns next to the silhouette), so a wave's live rays spread
+// along the face, its probe box spans hundreds of bricks and its chunk boxes stage only partially:
+// before round 6 such a block marched its ~7000 empty samples per ray with global gathers, up to
+// 55 ms.  The lane walks its run in segments of at most 4 texels per axis; a segment's box (its end
+// points' cells widened by `off`, the probe margin, as probe_run's box) spans at most 2 bricks per
+// axis, whose bytes are ORed.  Consecutive segments share their end points bit for bit (both from the
+// same expression), so the segments cover the run's box end to end.  Returns 0 if all are empty.
+// No wave operations inside, every launch constant an argument.
+__device__ __forceinline__ uint32_t probe_lane_walk(const uint8_t *occ, uint32_t obx, uint32_t obxy, float a0x, float a0y,
                                                   float a0z, float a1x, float a1y, float a1z, float ox, float oy,
                                                   float oz, int nx, int ny, int nz) {
   const float a0[3] = {a0x, a0y, a0z}, a1[3] = {a1x, a1y, a1z}, off[3] = {ox, oy, oz};
   const int n[3] = {nx, ny, nz};
   const float span = fmaxf(fabsf(a1x - a0x), fmaxf(fabsf(a1y - a0y), fabsf(a1z - a0z)));
-  const int nseg = max(1, (int)ceilf(span * (1.f / VR_LANE_SEG)));
+  const int nseg = max(1, (int)ceilf(span * (1.f / 4.0f)));
   const float inv = 1.f / (float)nseg;
   uint32_t v = 0;
   for (int j = 0; j < nseg && v == 0u; ++j) {
@@ -743,29 +629,6 @@ __device__ VR_LANES_ATTR uint32_t probe_lane_walk(const uint8_t *occ, uint32_t o
   }
   return v;
 }
-__device__ __forceinline__ int probe_lanes(const RenderParams &P, KParams kp0, bool alive, const f3 &pos,
-                                           const f3 &step, float t, float tfar, int L) {
-  // (every launch constant read through the argument segment at its point of use: the probe is rare,
-  // and values held for it across the sample loop would cost the loop registers)
-  const KParams kp = kparams_fresh(kp0);
-  uint32_t v = 0;
-  if (alive) {
-    const float rem = (tfar - t) / kp->tstep;  // as probe_run
-    const int s_eff = (rem < (float)L) ? max((int)rem + 2, 1) : L;
-    const float k = (float)(s_eff - 1);
-    const f3 pe = mk(fmaf(step.x, k, pos.x), fmaf(step.y, k, pos.y), fmaf(step.z, k, pos.z));
-    v = probe_lane_walk(kp->occ, kp->occ_bx, kp->occ_bxy,
-                        ((pos.x - kp->bmin[0]) * kp->bscale[0]) * kp->em.fnx - 0.5f,
-                        ((pos.y - kp->bmin[1]) * kp->bscale[1]) * kp->em.fny - 0.5f,
-                        ((pos.z - kp->bmin[2]) * kp->bscale[2]) * kp->em.fnz - 0.5f,
-                        ((pe.x - kp->bmin[0]) * kp->bscale[0]) * kp->em.fnx - 0.5f,
-                        ((pe.y - kp->bmin[1]) * kp->bscale[1]) * kp->em.fny - 0.5f,
-                        ((pe.z - kp->bmin[2]) * kp->bscale[2]) * kp->em.fnz - 0.5f, kp->probe_off[0],
-                        kp->probe_off[1], kp->probe_off[2], kp->em.nx, kp->em.ny, kp->em.nz);
-  }
-  return __any(v != 0u) ? 0 : 1;
-}
-
 // The empty-chunk leap: every tap of the chunk lies in the staged all-zero box, so each sample has
 // em = ab = 0, alpha = 1 - exp(-0) = 0 and adds exactly 0 (skip_empty proves the shading term
 // finite).  Only the march recurrences run, in the reference's order.
