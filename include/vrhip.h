@@ -569,6 +569,76 @@ int vr_slice_oblique(const uint64_t dims[3], const float element_size_um[3], con
                      const double normal_um[3], const double up_um[3], double pixel_um, uint64_t H, uint64_t W,
                      uint64_t thickness, vr_slice *out);
 
+/* --- volume histogram and per-label statistics of a resident source texture (no reference counterpart;
+ * MATLAB's histcounts(Data(:)) on the host array) -------------------------------------------------------
+ * The numbers an isosurface level, a transfer function's limits or a label gain are chosen from, taken
+ * from what the renderer holds -- typed uploads widened, label gains applied -- not from the host array.
+ * Voxels.  The d0*d1*d2 interior voxels of the source texture's padded resident buffer; apron voxels are
+ * never counted.  The source is resolved exactly as vr_render_slice resolves it (slot indices, alias rule,
+ * module-global bindings).  A 1x1x1 texture contributes its one voxel; an unbound texture contributes
+ * nothing: all counts 0, every total 0, min = max = NaN, sum = 0.
+ * Class of a voxel v, in fp32 with every operation rounded once (csrc/vr_histogram.h, one inline function
+ * that the kernel and vr_histogram_bin_host both evaluate), inv = 1.0f / (hi - lo) formed once on the host:
+ *   NaN -> nan;  v < lo -> below;  v > hi -> above;  otherwise
+ *   x = ((v - lo) * inv) * (float)nbins,  b = min((int)x, nbins - 1)
+ * so v == hi falls in the last bin, as MATLAB's histcounts does.  ninf counts the +-inf voxels, which are
+ * also counted in below / above.  total = nan + below + above + the sum of the row's bins.
+ * Extrema.  min / max over the row's non-NaN voxels, inf included, compared in IEEE totalOrder (-0 below
+ * +0), so the result bits do not depend on the visiting order; NaN for both in a row without such a voxel.
+ * Sum.  The double-precision sum of the row's finite voxels (the conversion from fp32 is exact); the order
+ * of the additions is the kernel's own and may differ between runs -- the one field that is not
+ * reproducible bit for bit.
+ * Rows.  label_count = 0: one row, the labels are not read.  label_count = n in 1..256: the voxel with
+ * label l goes to row (uint8)(l - label_first) < n ? l - label_first : n, i.e. rows 0..n-1 are the labels
+ * label_first .. label_first+n-1 and row n collects every other label; rows = n + 1.  This needs resident
+ * labels (vr_sync_labels) whose dims equal the source texture's.
+ * Clip.  With use_clip and planes set on the handle (vr_set_clip) only voxels whose centre every plane
+ * keeps are counted: q_j = ((float)i_j + 0.5f) / (float)d_j (one IEEE division per axis), kept iff
+ * fmaf(n2, q2, fmaf(n1, q1, fmaf(n0, q0, offset))) >= 0 for every plane as it was set (a NaN is not kept).
+ * With no planes set use_clip changes nothing.
+ * Outputs.  counts[r * nbins + b], fully overwritten by each call; rows_out[r] (may be NULL).  The device
+ * variant is asynchronous on `stream` and registers its reads of the source buffer and of the labels like
+ * the other *_device calls, so a label-gain rewrite or a label upload waits for it; d_rows holds final
+ * floats, not keys.
+ * Errors, checked before the handle (no device needed), each VR_ERR_ARGUMENT: q NULL; an unknown source;
+ * nbins outside 1 .. VR_HIST_MAX_BINS; non-finite limits, !(lo < hi), hi - lo or 1 / (hi - lo) not finite;
+ * label_first outside 0..255, label_count outside 0..256 or label_first + label_count > 256;
+ * rows * nbins > VR_HIST_MAX_CELLS; use_clip not 0 / 1; counts / d_counts NULL.  label_count > 0 without
+ * resident labels, or with labels whose dims differ from the source's, is VR_ERR_ARGUMENT with a message
+ * that names the labels.  A multi-device group handle is VR_ERR_UNSUPPORTED.  The call writes nothing of
+ * the handle's state: a 'render' before and after it gives the same bits.  VR_HIST_UNIFORM=0|1 (a test
+ * switch) forces the kernel's wave-uniform shortcut off or on; no count depends on it. */
+#define VR_HIST_MAX_BINS  4096
+#define VR_HIST_MAX_CELLS 12288          /* rows * nbins; 48 KiB of uint32 in LDS */
+typedef struct vr_histogram {
+  int32_t source;       /* vr_slice_source: EMISSION / ABSORPTION / REFLECTION, resolved exactly as vr_render_slice does */
+  int32_t nbins;        /* 1 .. VR_HIST_MAX_BINS */
+  float   lim[2];       /* lo < hi, both finite, hi - lo finite */
+  int32_t label_first;  /* 0 .. 255 */
+  int32_t label_count;  /* 0: one row, labels not read.  n in 1..256: rows 0..n-1 are labels
+                           label_first .. label_first+n-1, row n collects every other label; rows = n + 1 */
+  int32_t use_clip;     /* 0 / 1: count only voxels whose centre the handle's clip planes keep */
+  int32_t reserved;
+} vr_histogram;
+typedef struct vr_hist_row {
+  uint64_t total, below, above, nan, ninf;
+  float min, max;
+  double sum;
+} vr_hist_row;
+
+/* Into the caller-owned host arrays counts[rows * nbins] and, where not NULL, rows_out[rows]. */
+int vr_volume_histogram(vr_context *h, const vr_histogram *q, uint64_t *counts /* [rows][nbins] */,
+                        vr_hist_row *rows_out /* [rows], may be NULL */);
+
+/* Into device memory on `stream` (asynchronous, as vr_render_device). */
+int vr_volume_histogram_device(vr_context *h, const vr_histogram *q, unsigned long long *d_counts,
+                               vr_hist_row *d_rows /* may be NULL */, void *stream);
+
+/* The class rule above on the CPU (needs no device): bin[i] = the bin of v[i], or -1 below, -2 above,
+ * -3 NaN, for m values.  The nbins and limit checks above; a NULL v, bin or lim with m > 0 is
+ * VR_ERR_ARGUMENT. */
+int vr_histogram_bin_host(const float *v, uint64_t m, int32_t nbins, const float lim[2], int32_t *bin /* [m] */);
+
 /* The kernel's table lookup on the CPU (needs no device): out[k * m + j] = L(table plane k, n, lim,
  * c[j]) for the ncomp planes table[k * n + i].  VR_ERR_ARGUMENT for a NULL pointer with m > 0, an n
  * outside 2..VR_TF_MAX_ENTRIES, ncomp < 1, or limits that are not finite with lo < hi. */

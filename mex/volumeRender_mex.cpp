@@ -320,6 +320,59 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     if (nlhs > 2) plhs[2] = lab; else mxDestroyArray(lab);
     return;
   }
+  if (!strcmp(cmd, "volume_histogram")) {
+    // volumeRender('volume_histogram', h, source, nbins, single([lo hi]), int32([first count]), use_clip)
+    // -> [counts, summary] (vr_volume_histogram): source 'emission' | 'absorption' | 'reflection' (or its
+    // code), count = 0: one row; counts uint64 [nbins rows] (counts(:, r) is row r), summary double
+    // [rows 8] = total, below, above, nan, ninf, min, max, sum per row
+    if (nlhs > 2) mexErrMsgTxt("Too many output arguments.");
+    if (nrhs < 7) mexErrMsgTxt("insufficient parameter!");
+    if (nrhs > 7) mexErrMsgTxt("volume_histogram: too many input arguments");
+    vr_histogram q{};
+    static const char *const sources[3] = {"emission", "absorption", "reflection"};
+    q.source = -1;  // an unknown name or code stays invalid, which the library refuses
+    if (mxGetClassID(prhs[2]) == mxCHAR_CLASS) {
+      char buf[16];
+      if (!mxGetString(prhs[2], buf, sizeof(buf)))
+        for (int i = 0; i < 3; ++i)
+          if (!strcmp(buf, sources[i])) q.source = i;
+    } else {
+      if (mxGetNumberOfElements(prhs[2]) != 1 || mxIsComplex(prhs[2]))
+        mexErrMsgTxt("volume_histogram: source must be 'emission', 'absorption', 'reflection' or a code");
+      const double v = mxGetScalar(prhs[2]);
+      if (v >= 0.0 && v < 3.0 && v == (double)(int32_t)v) q.source = (int32_t)v;
+    }
+    if (mxGetNumberOfElements(prhs[3]) != 1 || mxIsComplex(prhs[3])) mexErrMsgTxt("volume_histogram: nbins must be a real scalar");
+    const double nb = mxGetScalar(prhs[3]);
+    q.nbins = (nb >= 1.0 && nb <= (double)VR_HIST_MAX_BINS && nb == (double)(int32_t)nb) ? (int32_t)nb : 0;  // (0: refused below)
+    if (mxGetClassID(prhs[4]) != mxSINGLE_CLASS || mxIsComplex(prhs[4]) || mxGetNumberOfElements(prhs[4]) != 2)
+      mexErrMsgTxt("volume_histogram: limits must be a single vector [lo hi]");
+    memcpy(q.lim, mxGetData(prhs[4]), sizeof(q.lim));
+    if (mxGetClassID(prhs[5]) != mxINT32_CLASS || mxGetNumberOfElements(prhs[5]) != 2)
+      mexErrMsgTxt("volume_histogram: labels must be an int32 vector [first count]");
+    const int32_t *lab = static_cast<const int32_t *>(mxGetData(prhs[5]));
+    q.label_first = lab[0];
+    q.label_count = lab[1];
+    if (mxGetNumberOfElements(prhs[6]) != 1 || mxIsComplex(prhs[6])) mexErrMsgTxt("volume_histogram: use_clip must be a scalar");
+    const double uc = mxGetScalar(prhs[6]);
+    q.use_clip = uc == 0.0 ? 0 : (uc == 1.0 ? 1 : -1);
+    const bool sized = q.nbins >= 1 && q.label_count >= 0 && q.label_count <= 256;  // (else refused, with its message)
+    const mwSize rows = sized ? (mwSize)(q.label_count > 0 ? q.label_count + 1 : 1) : 1;
+    const mwSize nbins = sized ? (mwSize)q.nbins : 1;
+    mxArray *counts = mxCreateNumericMatrix(nbins, rows, mxUINT64_CLASS, mxREAL);
+    std::vector<vr_hist_row> rr(rows);
+    check(vr_volume_histogram(h, &q, static_cast<uint64_t *>(mxGetData(counts)), rr.data()));
+    mxArray *summary = mxCreateNumericMatrix(rows, 8, mxDOUBLE_CLASS, mxREAL);
+    double *s = static_cast<double *>(mxGetData(summary));
+    for (mwSize r = 0; r < rows; ++r) {
+      const double col[8] = {(double)rr[r].total, (double)rr[r].below, (double)rr[r].above, (double)rr[r].nan,
+                             (double)rr[r].ninf,  (double)rr[r].min,   (double)rr[r].max,   rr[r].sum};
+      for (int c = 0; c < 8; ++c) s[(size_t)c * rows + r] = col[c];
+    }
+    plhs[0] = counts;
+    if (nlhs > 1) plhs[1] = summary; else mxDestroyArray(summary);
+    return;
+  }
   if (!strcmp(cmd, "render_isosurface")) {
     // volumeRender('render_isosurface', h, <render args>, level) -> [img, depth, normal]
     // (vr_render_isosurface): the first-hit surface emission == level lit by the lights, the depth of

@@ -30,6 +30,9 @@ VR_LABEL_GAINS_MAX = 256
 VR_SLICE_MAX, VR_SLICE_MIN, VR_SLICE_SUM = 0, 1, 2
 VR_SLICE_EMISSION, VR_SLICE_ABSORPTION, VR_SLICE_REFLECTION = 0, 1, 2
 VR_SLICE_MAX_SAMPLES = 4096
+# vr_volume_histogram
+VR_HIST_MAX_BINS = 4096
+VR_HIST_MAX_CELLS = 12288
 # enum vr_launch_flag: the bits of vr_last_launch_flags, in bit order
 LAUNCH_FLAGS = ("tame", "small_x", "eds_finite", "skip_empty", "re_ok", "lut_ok", "tap_half", "ab_alias", "share",
                 "big", "occ")
@@ -76,6 +79,16 @@ class VrSlice(ctypes.Structure):
     _fields_ = [("origin", c_float * 3), ("du", c_float * 3), ("dv", c_float * 3), ("dw", c_float * 3),
                 ("resolution", c_uint64 * 2), ("samples", c_int32), ("mode", c_int32), ("source", c_int32),
                 ("reserved", c_int32)]
+
+
+class VrHistogram(ctypes.Structure):
+    _fields_ = [("source", c_int32), ("nbins", c_int32), ("lim", c_float * 2), ("label_first", c_int32),
+                ("label_count", c_int32), ("use_clip", c_int32), ("reserved", c_int32)]
+
+
+class VrHistRow(ctypes.Structure):
+    _fields_ = [("total", c_uint64), ("below", c_uint64), ("above", c_uint64), ("nan", c_uint64),
+                ("ninf", c_uint64), ("min", c_float), ("max", c_float), ("sum", ctypes.c_double)]
 
 
 class VrChannel(ctypes.Structure):
@@ -139,6 +152,9 @@ SIGNATURES = [
     ("vr_slice_oblique", c_int, [POINTER(c_uint64), POINTER(c_float), POINTER(ctypes.c_double),
                                  POINTER(ctypes.c_double), POINTER(ctypes.c_double), ctypes.c_double, c_uint64,
                                  c_uint64, c_uint64, POINTER(VrSlice)]),
+    ("vr_volume_histogram", c_int, [c_void_p, POINTER(VrHistogram), c_void_p, c_void_p]),
+    ("vr_volume_histogram_device", c_int, [c_void_p, POINTER(VrHistogram), c_void_p, c_void_p, c_void_p]),
+    ("vr_histogram_bin_host", c_int, [c_void_p, c_uint64, c_int32, POINTER(c_float), c_void_p]),
     ("vr_partition_columns", c_int64, [c_int64, POINTER(VrPartition)]),
     ("vr_assemble_partitions", c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int64, c_void_p,
                                        c_void_p]),

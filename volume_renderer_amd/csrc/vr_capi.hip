@@ -480,6 +480,44 @@ int vr_render_slice(vr_context *h, const vr_slice *s, float *out, float *out_aux
   VR_GUARD_END
 }
 
+int vr_volume_histogram_device(vr_context *h, const vr_histogram *q, unsigned long long *d_counts, vr_hist_row *d_rows,
+                               void *stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (int rc = check_histogram(q)) return rc;
+  if (!d_counts) return fail(VR_ERR_ARGUMENT, "histogram: counts is NULL");
+  VR_ENTRY_BEGIN(h, q)
+  return do_histogram(h, q, d_counts, d_rows, (hipStream_t)stream);
+  VR_GUARD_END
+}
+
+int vr_volume_histogram(vr_context *h, const vr_histogram *q, uint64_t *counts, vr_hist_row *rows_out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (int rc = check_histogram(q)) return rc;
+  if (!counts) return fail(VR_ERR_ARGUMENT, "histogram: counts is NULL");
+  VR_ENTRY_BEGIN(h, q)
+  // the counts and, behind them, the rows in the handle's output buffer
+  const size_t rows = (size_t)histogram_rows(q);
+  const size_t cbytes = rows * (size_t)q->nbins * sizeof(unsigned long long);
+  ensure_out(h, cbytes + rows * sizeof(vr_hist_row));
+  unsigned long long *d_counts = reinterpret_cast<unsigned long long *>(h->d_out);
+  vr_hist_row *d_rows = rows_out ? reinterpret_cast<vr_hist_row *>(reinterpret_cast<char *>(h->d_out) + cbytes) : nullptr;
+  const int rc = do_histogram(h, q, d_counts, d_rows, nullptr);
+  if (rc) return rc;
+  VR_HIP(hipMemcpy(counts, d_counts, cbytes, hipMemcpyDeviceToHost));
+  if (rows_out) VR_HIP(hipMemcpy(rows_out, d_rows, rows * sizeof(vr_hist_row), hipMemcpyDeviceToHost));
+  return VR_OK;
+  VR_GUARD_END
+}
+
+int vr_histogram_bin_host(const float *v, uint64_t m, int32_t nbins, const float lim[2], int32_t *bin) {
+  if (m && (!v || !bin)) return fail(VR_ERR_ARGUMENT, "histogram: v / bin is NULL");
+  if (!lim) return fail(VR_ERR_ARGUMENT, "histogram: lim is NULL");
+  if (int rc = check_hist_bins(nbins, lim)) return rc;
+  const float inv = 1.0f / (lim[1] - lim[0]);
+  for (uint64_t i = 0; i < m; ++i) bin[i] = vr_hist_bin(v[i], lim[0], lim[1], inv, nbins);
+  return VR_OK;
+}
+
 static int check_slice_count(uint64_t thickness) {
   if (thickness < 1 || thickness > VR_SLICE_MAX_SAMPLES)
     return fail(VR_ERR_ARGUMENT, "slice: thickness must be 1 .. " + std::to_string(VR_SLICE_MAX_SAMPLES));

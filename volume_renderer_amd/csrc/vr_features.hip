@@ -1,5 +1,8 @@
 // vr_features.hip -- the feature renders on the host (vr_host.h): projection, slice, isosurface and
-// transfer-function render, each on the frame of build_frame (vr_frame.hip) and its own kernel file.
+// transfer-function render, each on the frame of build_frame (vr_frame.hip) and its own kernel file, and
+// the volume histogram (no frame: one source texture, as the slice).
+#include <cassert>
+
 #include "vr_host.h"
 #include "vr_transfer.h"
 
@@ -122,6 +125,107 @@ int do_slice(vr_context *h, const vr_slice *s, float *d_out, float *d_aux, float
   VR_HIP(vr::launch_slice(S, s->mode, big, stream));
   VR_HIP(L.finish());
   if (labels) {
+    vr_host::EventPtr ev;
+    if (vr_host::record_event(stream, ev) == hipSuccess) h->labels_readers.add(ev);
+    else VR_HIP(hipStreamSynchronize(stream));
+  }
+  return VR_OK;
+}
+
+// The argument checks of vr_volume_histogram (include/vrhip.h): before the handle, no device needed.
+int check_hist_bins(int32_t nbins, const float lim[2]) {
+  if (nbins < 1 || nbins > VR_HIST_MAX_BINS)
+    return fail(VR_ERR_ARGUMENT, "histogram: 1 .. " + std::to_string(VR_HIST_MAX_BINS) + " bins");
+  if (!std::isfinite(lim[0]) || !std::isfinite(lim[1]) || !(lim[0] < lim[1]))
+    return fail(VR_ERR_ARGUMENT, "histogram: limits must be finite with lo < hi");
+  const float w = lim[1] - lim[0];
+  if (!std::isfinite(w) || !std::isfinite(1.0f / w))
+    return fail(VR_ERR_ARGUMENT, "histogram: hi - lo and 1 / (hi - lo) must be finite in fp32");
+  return VR_OK;
+}
+int32_t histogram_rows(const vr_histogram *q) { return q->label_count > 0 ? q->label_count + 1 : 1; }
+int check_histogram(const vr_histogram *q) {
+  if (!q) return fail(VR_ERR_ARGUMENT, "histogram: the query is NULL");
+  if (q->source != VR_SLICE_EMISSION && q->source != VR_SLICE_ABSORPTION && q->source != VR_SLICE_REFLECTION)
+    return fail(VR_ERR_ARGUMENT, "histogram: unknown source");
+  if (int rc = check_hist_bins(q->nbins, q->lim)) return rc;
+  if (q->label_first < 0 || q->label_first > 255 || q->label_count < 0 || q->label_count > 256 ||
+      q->label_first + q->label_count > 256)
+    return fail(VR_ERR_ARGUMENT, "histogram: label_first 0 .. 255, label_count 0 .. 256, first + count <= 256");
+  if ((int64_t)histogram_rows(q) * q->nbins > VR_HIST_MAX_CELLS)
+    return fail(VR_ERR_ARGUMENT, "histogram: rows * nbins must not exceed " + std::to_string(VR_HIST_MAX_CELLS));
+  if (q->use_clip != 0 && q->use_clip != 1) return fail(VR_ERR_ARGUMENT, "histogram: use_clip must be 0 or 1");
+  return VR_OK;
+}
+
+// Volume histogram (vr_volume_histogram, vr_histogram.hip): the DevTex of the one source texture through
+// the slot indices, as do_slice resolves it; the clip planes as they were set (q is the kernel's own
+// coordinate, no conversion).  The counts and the row accumulators are zeroed on the launch's stream --
+// the accumulators as a zero blob through the launch's staged constants -- then the count launch and,
+// for d_rows, the finalize launch.  Nothing of the handle, the texture unit or the last launch flags is
+// written.  The kernel's wave-uniform shortcut is off -- it won on the zero-heavy volume and lost on the
+// incoherent one -- unless VR_HIST_UNIFORM=0|1 (test switch) forces either side.
+#define VR_HIST_UNIFORM_DEFAULT false
+static bool hist_uniform() {
+  if (const char *ev = test_env("VR_HIST_UNIFORM")) {
+    if (ev[0] == '0') return false;
+    if (ev[0] == '1') return true;
+  }
+  return VR_HIST_UNIFORM_DEFAULT;
+}
+int do_histogram(vr_context *h, const vr_histogram *q, unsigned long long *d_counts, vr_hist_row *d_rows,
+                 hipStream_t stream) {
+  if (!d_counts) return fail(VR_ERR_ARGUMENT, "histogram: counts is NULL");
+  vr::HistParams H{};
+  H.rows = histogram_rows(q);
+  H.nbins = q->nbins;
+  const int32_t slot = q->source == VR_SLICE_EMISSION ? g_tex.idx_em
+                       : q->source == VR_SLICE_ABSORPTION ? g_tex.idx_ab : g_tex.idx_re;
+  H.tex = dev_tex(g_tex.bind[slot]);  // (getTexture, kernel.cu:127-144)
+  const bool bound = H.tex.p && H.tex.nx > 0 && H.tex.ny > 0 && H.tex.nz > 0;
+  const bool labels = q->label_count > 0;
+  if (labels) {
+    if (!h->d_labels || !h->labels_bytes)
+      return fail(VR_ERR_ARGUMENT, "histogram: rows by label need resident labels (vr_sync_labels)");
+    if (bound && (h->labels_dims[0] != (uint64_t)H.tex.nx || h->labels_dims[1] != (uint64_t)H.tex.ny ||
+                  h->labels_dims[2] != (uint64_t)H.tex.nz)) {
+      std::ostringstream os;
+      os << "histogram: the labels' dims [" << h->labels_dims[0] << " " << h->labels_dims[1] << " "
+         << h->labels_dims[2] << "] differ from the source texture's [" << H.tex.nx << " " << H.tex.ny << " "
+         << H.tex.nz << "]";
+      return fail(VR_ERR_ARGUMENT, os.str());
+    }
+    H.labels = h->d_labels;
+  }
+  H.lo = q->lim[0];
+  H.hi = q->lim[1];
+  H.inv = 1.0f / (q->lim[1] - q->lim[0]);
+  H.label_first = q->label_first;
+  H.label_count = q->label_count;
+  if (q->use_clip)
+    for (int32_t i = 0; i < h->nclip; ++i) {
+      for (int c = 0; c < 3; ++c) H.clip.pl[i][c] = h->clip[i].normal[c];
+      H.clip.pl[i][3] = h->clip[i].offset;
+      H.clip.n = i + 1;
+    }
+  H.counts = d_counts;
+  LaunchRec L = launch_rec(h, stream);
+  VR_HIP(hipMemsetAsync(d_counts, 0, (size_t)H.rows * (size_t)H.nbins * sizeof(unsigned long long), stream));
+  const std::vector<char> zeros(vr::hist_acc_bytes(H.rows), 0);
+  const void *d_acc = nullptr;
+  VR_HIP(L.stage(zeros.data(), zeros.size(), &d_acc));
+  H.acc = const_cast<void *>(d_acc);
+  if (bound) {
+    // no workgroup may see 2^32 voxels: its 32-bit LDS cells could wrap
+    const uint64_t nrows = (uint64_t)H.tex.ny * (uint64_t)H.tex.nz;
+    const uint64_t blocks = vr::histogram_blocks(nrows, (uint64_t)H.tex.nx);
+    assert(((nrows + blocks - 1) / blocks) * (uint64_t)H.tex.nx < (1ull << 32));
+    (void)blocks;
+    VR_HIP(vr::launch_histogram(H, hist_uniform(), stream));
+  }
+  if (d_rows) VR_HIP(vr::launch_histogram_finalize(d_counts, H.acc, H.rows, H.nbins, d_rows, stream));
+  VR_HIP(L.finish());
+  if (labels && bound) {
     vr_host::EventPtr ev;
     if (vr_host::record_event(stream, ev) == hipSuccess) h->labels_readers.add(ev);
     else VR_HIP(hipStreamSynchronize(stream));

@@ -5,7 +5,7 @@
 //   vr_sync.hip      upload and slot state machine, memory checks, label gains, do_sync_volumes
 //   vr_frame.hip     clip conversion, build_frame, lights, partition, depth lanes, the march entry table, schedules
 //   vr_render.hip    do_render, do_render_slab, the multi-device group, view sets / channels
-//   vr_features.hip  projection, slice, isosurface and transfer renders
+//   vr_features.hip  projection, slice, isosurface and transfer renders, the volume histogram
 //   vr_capi.hip      the extern "C" entries of include/vrhip.h
 #pragma once
 
@@ -409,6 +409,11 @@ int do_project(vr_context *h, const vr_render_args *a, int32_t mode, const vr_pa
                float *d_aux, unsigned long long *d_steps, hipStream_t stream);
 int check_slice(const vr_slice *s);
 int do_slice(vr_context *h, const vr_slice *s, float *d_out, float *d_aux, float *d_lab, hipStream_t stream);
+int check_hist_bins(int32_t nbins, const float lim[2]);
+int check_histogram(const vr_histogram *q);
+int32_t histogram_rows(const vr_histogram *q);
+int do_histogram(vr_context *h, const vr_histogram *q, unsigned long long *d_counts, vr_hist_row *d_rows,
+                 hipStream_t stream);
 int do_isosurface(vr_context *h, const vr_render_args *a, float level, const vr_partition *part, float *d_out,
                   float *d_depth, float *d_normal, unsigned long long *d_steps, hipStream_t stream);
 int check_transfer(const vr_transfer *tf);

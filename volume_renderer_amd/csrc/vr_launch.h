@@ -10,6 +10,7 @@
 
 #include "vr_clip.h"
 #include "vr_device.h"
+#include "vr_histogram.h"
 #include "vr_slice.h"
 
 #ifndef VR_WITH_K8
@@ -65,6 +66,12 @@ hipError_t launch_occupancy(const float *p, uint32_t px, uint32_t py, uint32_t p
                             hipStream_t s);
 // vr_slice.hip: mode = vr_slice_mode
 hipError_t launch_slice(const SliceParams &S, int mode, bool big, hipStream_t s);
+// vr_histogram.hip: the count launch into H.counts / H.acc (zeroed on s before; uniform: the wave-uniform
+// shortcut), its grid for nrows rows of nx voxels, and the finalize launch that writes rows vr_hist_row
+hipError_t launch_histogram(const HistParams &H, bool uniform, hipStream_t s);
+uint64_t histogram_blocks(uint64_t nrows, uint64_t nx);
+hipError_t launch_histogram_finalize(const unsigned long long *counts, const void *acc, int32_t rows, int32_t nbins,
+                                     void *rows_out, hipStream_t s);
 // vr_labels.hip: dst = src under the n gains of `gains` by the dense label bytes; *st += the statistics of dst
 hipError_t launch_label_gain(const float *src, const uint8_t *labels, const float *gains, int32_t n, int32_t nx,
                              int32_t ny, int32_t nz, float *dst, BufStats *st, hipStream_t s);

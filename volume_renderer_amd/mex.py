@@ -605,6 +605,70 @@ def render_slice_device(handle, s, d_out: int, d_aux: int = 0, d_labels: int = 0
                                        ctypes.c_void_p(int(stream)) if stream else None))
 
 
+# numpy view of vr_hist_row (include/vrhip.h), and the column order of the mex command's summary
+HIST_ROW_DTYPE = np.dtype([("total", "<u8"), ("below", "<u8"), ("above", "<u8"), ("nan", "<u8"), ("ninf", "<u8"),
+                           ("min", "<f4"), ("max", "<f4"), ("sum", "<f8")])
+HIST_SUMMARY = ("total", "below", "above", "nan", "ninf", "min", "max", "sum")
+
+
+def make_histogram(source, nbins, limits, labels=None, use_clip=0) -> _lib.VrHistogram:
+    """A vr_histogram from the mex command's arguments: source as a string or code, nbins, limits single
+    [lo hi], labels int32 [first count] (count 0, or None: one row, labels not read), use_clip 0 / 1 / false /
+    true.  The library checks the values."""
+    lim = np.asarray(limits)
+    if lim.dtype != np.float32 or lim.size != 2:
+        raise _lib.VrError(1, "volume_histogram: limits must be a single vector [lo hi]")
+    lab = np.int32([0, 0]) if labels is None else np.asarray(labels)
+    if lab.dtype != np.int32 or lab.size != 2:
+        raise _lib.VrError(1, "volume_histogram: labels must be an int32 vector [first count]")
+    q = _lib.VrHistogram()
+    q.source = slice_source(source)
+    q.nbins = int(np.asarray(nbins).reshape(-1)[0])
+    q.lim[0], q.lim[1] = lim.reshape(-1)
+    q.label_first, q.label_count = (int(x) for x in lab.reshape(-1))
+    q.use_clip = int(np.asarray(use_clip).reshape(-1)[0])
+    return q
+
+
+def histogram_rows(q) -> int:
+    """Rows of a vr_histogram's tables: label_count + 1, or 1 without labels."""
+    return q.label_count + 1 if q.label_count > 0 else 1
+
+
+def volume_histogram(handle, q):
+    """vr_volume_histogram: (counts uint64 [rows, nbins], rows as a HIST_ROW_DTYPE record array [rows])."""
+    rows = histogram_rows(q)
+    if not (1 <= q.nbins <= _lib.VR_HIST_MAX_BINS and 1 <= rows <= 257):  # the library says why
+        rows, nb = 1, 1
+    else:
+        nb = q.nbins
+    counts = np.zeros((rows, nb), dtype=np.uint64)
+    summ = np.zeros(rows, dtype=HIST_ROW_DTYPE)
+    check(lib().vr_volume_histogram(_handle(handle), ctypes.byref(q), counts.ctypes.data_as(ctypes.c_void_p),
+                                    summ.ctypes.data_as(ctypes.c_void_p)))
+    return counts, summ
+
+
+def volume_histogram_device(handle, q, d_counts: int, d_rows: int = 0, stream: int = 0) -> None:
+    """A histogram into device memory (vr_volume_histogram_device), asynchronous on `stream`: q from
+    make_histogram; d_counts uint64 [rows][nbins]; d_rows rows vr_hist_row records of 56 bytes, 0: none."""
+    check(lib().vr_volume_histogram_device(_handle(handle), ctypes.byref(q),
+                                           ctypes.c_void_p(int(d_counts)) if d_counts else None,
+                                           ctypes.c_void_p(int(d_rows)) if d_rows else None,
+                                           ctypes.c_void_p(int(stream)) if stream else None))
+
+
+def histogram_bin_host(v, nbins: int, limits) -> np.ndarray:
+    """vr_histogram_bin_host: the kernel's class rule on the CPU -- per value its bin, or -1 below, -2 above,
+    -3 NaN."""
+    a = np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
+    lim = (ctypes.c_float * 2)(*[float(x) for x in np.asarray(limits, np.float32).reshape(-1)[:2]])
+    out = np.zeros(a.size, dtype=np.int32)
+    check(lib().vr_histogram_bin_host(a.ctypes.data_as(ctypes.c_void_p) if a.size else None, a.size, int(nbins), lim,
+                                      out.ctypes.data_as(ctypes.c_void_p) if a.size else None))
+    return out
+
+
 def set_option(name: str, value: int) -> None:
     """vr_set_option: a process-wide library option (include/vrhip.h)."""
     check(lib().vr_set_option(name.encode(), int(value)))
@@ -751,7 +815,8 @@ def _group_devices():
 def volumeRender(cmd, *args):
     """The `volumeRender` mex: commands 'new', 'delete', 'mem_info', 'sync_volumes', 'render' (and
     'render_stereo', 'render_channels', 'render_projection', 'render_isosurface', 'render_transfer',
-    'render_slice', 'set_clip', 'sync_labels', 'set_label_gains', which the reference does not have)."""
+    'render_slice', 'volume_histogram', 'set_clip', 'sync_labels', 'set_label_gains', which the reference does
+    not have)."""
     nrhs = 1 + len(args)
     if not isinstance(cmd, str) or len(cmd) >= 64:
         raise _lib.VrError(1, "First input should be a command string less than 64 characters long.")
@@ -872,6 +937,15 @@ def volumeRender(cmd, *args):
         check(L.vr_render_slice(h, ctypes.byref(s), *(p.ctypes.data_as(ctypes.c_void_p) if p.size else None
                                                       for p in (img, aux, lab))))
         return img, aux, lab
+    if cmd == "volume_histogram":  # ('volume_histogram', h, source, nbins, single([lo hi]), int32([first count]), use_clip)
+        if nrhs < 7:
+            raise _lib.VrError(1, "insufficient parameter!")
+        if nrhs > 7:
+            raise _lib.VrError(1, "volume_histogram: too many input arguments")
+        counts, summ = volume_histogram(args[0], make_histogram(*args[1:6]))
+        # counts [nbins, rows] column-major: counts(:, r) is row r; summary [rows, 8] double
+        summary = np.asfortranarray(np.stack([summ[k].astype(np.float64) for k in HIST_SUMMARY], axis=1))
+        return np.asfortranarray(counts.T), summary
     if cmd == "render_isosurface":  # ('render_isosurface', h, <the nine render arguments>, level)
         if nrhs < 12:
             raise _lib.VrError(1, "insufficient parameter!")

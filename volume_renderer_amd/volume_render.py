@@ -314,6 +314,28 @@ class VolumeRender:
         out = (img,) + ((plane,) if aux else ()) + ((lab,) if labels else ())
         return out if len(out) > 1 else img
 
+    def histogram(self, nbins, limits, source="emission", labels=None, use_clip=False):
+        """Histogram and statistics of a resident volume (vr_volume_histogram): of what the renderer holds
+        -- a typed upload widened, label gains applied -- not of the host array.  `nbins` equal bins over
+        `limits` [lo hi] (v == hi in the last bin, as histcounts); `source` 'emission' | 'absorption' |
+        'reflection'.  labels=None: one row over every voxel.  labels=(first, count): one row per label
+        first .. first+count-1 of VolumeLabels (0-based label values) and a last row for every other
+        label.  use_clip=True counts only the voxels whose centre the ClipPlanes keep.
+        Returns (counts, summary): counts uint64 [nbins, rows] (counts[:, r] is row r), summary a dict
+        of per-row arrays total, below, above, nan, ninf (uint64), min, max (single; NaN in a row without
+        a non-NaN voxel) and sum (double, over the finite voxels)."""
+        from . import mex
+        first, count = (0, 0) if labels is None else (int(labels[0]), int(labels[1]))
+        self._validate_volumes()
+        self._apply_clip()
+        self._apply_labels()
+        self.syncVolumes()
+        counts, s = volumeRender("volume_histogram", self.objectHandle, source, np.int32(nbins),
+                                 np.asarray(limits, np.float32).reshape(-1), np.int32([first, count]), bool(use_clip))
+        summary = {k: s[:, i].astype(np.uint64 if i < 5 else (np.float32 if i < 7 else np.float64))
+                   for i, k in enumerate(mex.HIST_SUMMARY)}
+        return counts, summary
+
     def renderIsosurface(self, level, aux=False):
         """The first-hit isosurface VolumeEmission == level through the current camera
         (vr_render_isosurface): the opaque surface lit by LightSources / VolumeIllumination plus
