@@ -484,6 +484,58 @@ int vr_get_label_gains(vr_context *h, float *gains /* 256 */, int32_t *n);
 int vr_label_gain_host(const float *src, const uint8_t *labels, const float *gains, int32_t n, uint64_t count,
                        float *dst);
 
+/* --- Gaussian smoothing of the resident emission volume (no reference counterpart; the usual first step
+ * on a noisy stack is imgaussfilt3(Data, sigma) on the host and a full re-upload) ----------------------
+ * sigma[j], in voxels along dims[j] of Data (the axis order of the clip planes' normals), is state of the
+ * handle.  The resident emission buffer, its upload statistics and its occupancy map are re-derived on the
+ * device from the unmodified upload -- the derivation of the label gains, with the smoothing in front:
+ * unmodified upload -> smoothing -> label gains -> resident buffer.  Every render, slice and histogram
+ * call reads an ordinary resident volume and is unchanged.
+ * Value.  The weights of one axis are formed once on the host in double: R = (int)ceil(2.0 * (double)sigma),
+ * g_i = exp(-(double)(i*i) / (2 sigma^2)) for i = -R..R, S the sum of the g_i in ascending i,
+ * w_k = (float)(g_{k-R} / S), k = 0..2R -- the shape of imgaussfilt3's defaults (size 2*ceil(2 sigma)+1,
+ * replicate padding); the arithmetic is this library's own.  One axis pass over a line x[0..n-1] is, in
+ * fp32 with every operation rounded once,
+ *     acc = w[0] * x[c(i-R)];  acc = fmaf(w[k], x[c(i-R+k)], acc) for k = 1..2R;  y[i] = acc
+ * with c clamping to 0..n-1.  The passes run along dims[0], then dims[1], then dims[2], each reading the
+ * fp32 result of the one before.  An axis with sigma[j] == 0 or dims[j] == 1 is skipped (2-D data needs no
+ * special call); with every axis skipped the buffer holds the unmodified voxels bit for bit.  NaN, inf,
+ * +-0 and subnormals follow IEEE through the chain; nothing is flushed or tested.  No bit depends on how
+ * the kernels tile or order their work: the library holds two kernel forms (one launch per axis, which
+ * serves every radius; all three axes fused in one launch, which measured slower and runs only under the
+ * test switch VR_SMOOTH_FORM=fused), and they give the same bits.  A label's gain multiplies the smoothed voxel: the result equals
+ * vr_label_gain_host applied to the output of vr_smooth_host.
+ * State left.  That of vr_sync_volumes of the host-filtered volume, bit for bit: the padded data with its
+ * apron (the edge replicate of the written interior), nonfinite and maxabs of the final values, a rebuilt
+ * occupancy map (the support grows by R), a new upload version.  What is smoothed is the buffer the
+ * handle's last vr_sync_volumes bound as emission; an absorption or reflection that aliases it follows; a
+ * separately uploaded volume, the gradient volumes of lookup mode and the LUT are not touched.
+ * When.  Eagerly inside vr_set_smoothing, at the end of vr_sync_volumes (also per channel in
+ * vr_render_channels), inside vr_sync_labels and vr_set_label_gains; nothing is written when nothing
+ * changed.  A rewrite waits for every launch that reads the buffer, so a *_device call in flight sees the
+ * volume it was launched on.  A failed pass leaves the unmodified upload behind, and a vr_set_smoothing that
+ * failed so leaves no sigma set.
+ * Memory.  While a sigma is set the one unmodified copy, shared with the label gains, counts in the
+ * handle's required memory; during a derivation of more than one pass one further scratch volume comes from
+ * the buffer pool and goes back afterwards.  When they do not fit: VR_ERR_VRAM, and the state stays as it
+ * was.  'mem_info' has a line for the smoothing while one is set.
+ * Errors.  Checked before the handle (they need no device), each VR_ERR_ARGUMENT: a NaN, negative or
+ * infinite sigma; a sigma above VR_SMOOTH_MAX_SIGMA.  VR_ERR_UNSUPPORTED, the message names the smoothing:
+ * a non-zero sigma on a multi-device group handle; vr_render_slab on a handle with smoothing set (a slab's
+ * z border would be clamped where the whole volume has neighbouring planes).  With no smoothing set every
+ * call allocates, uploads and launches what it does without this feature. */
+#define VR_SMOOTH_MAX_SIGMA 6.0f /* radius ceil(2 sigma) <= 12 */
+int vr_set_smoothing(vr_context *h, const float sigma[3]); /* NULL or all zero clears */
+int vr_get_smoothing(vr_context *h, float sigma[3]);
+
+/* The value rule above on the CPU (needs no device), by the inline functions the kernels evaluate
+ * (csrc/vr_smooth.h).  vr_smooth_weights_host: *radius = R and w[0..2R] for one sigma (room for 25;
+ * sigma = 0: R = 0, w[0] = 1).  vr_smooth_host: dst = src smoothed, both dense dims[0] x dims[1] x dims[2]
+ * column-major (dims[0] fastest); dst may be src.  The sigma checks of vr_set_smoothing; a NULL pointer is
+ * VR_ERR_ARGUMENT. */
+int vr_smooth_weights_host(float sigma, int32_t *radius, float *w /* room for 25 */);
+int vr_smooth_host(const float *src, const uint64_t dims[3], const float sigma[3], float *dst);
+
 /* --- slice views: axis-aligned, oblique and thick-slab sections of a resident volume (no reference
  * counterpart; MATLAB's sliceViewer / obliqueslice, a radiologist's MPR) ------------------------------
  * The sampler of every render evaluated on a plane instead of along camera rays: what the renderer shows

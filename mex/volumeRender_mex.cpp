@@ -529,5 +529,36 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     check(vr_set_label_gains(h, static_cast<const float *>(mxGetData(g)), (int32_t)mxGetNumberOfElements(g)));
     return;
   }
+  if (!strcmp(cmd, "set_smoothing")) {
+    // volumeRender('set_smoothing', h, sigma) (vr_set_smoothing): sigma in voxels, a single or double scalar
+    // (all three dimensions of Data) or 3-vector; [] or false clears.  The emission volume on the device
+    // follows at once; the sigma stays with the handle.
+    if (nlhs > 0) mexErrMsgTxt("Too many output arguments.");
+    if (nrhs < 3) mexErrMsgTxt("insufficient parameter!");
+    if (nrhs > 3) mexErrMsgTxt("set_smoothing: too many input arguments");
+    const mxArray *g = prhs[2];
+    const char *bad = "set_smoothing: sigma must be a single or double scalar or 3-vector, [] or false";
+    if (mxIsClass(g, "logical")) {
+      if (mxGetNumberOfElements(g) != 1 || mxGetScalar(g) != 0.0) mexErrMsgTxt(bad);
+      check(vr_set_smoothing(h, nullptr));
+      return;
+    }
+    const size_t n = mxGetNumberOfElements(g);
+    const bool f32 = mxGetClassID(g) == mxSINGLE_CLASS;
+    if ((!f32 && mxGetClassID(g) != mxDOUBLE_CLASS) || mxIsComplex(g) || mxGetNumberOfDimensions(g) != 2)
+      mexErrMsgTxt(bad);  // (an empty char or cell array is no sigma either)
+    if (n == 0) {
+      check(vr_set_smoothing(h, nullptr));
+      return;
+    }
+    if ((mxGetM(g) != 1 && mxGetN(g) != 1) || (n != 1 && n != 3)) mexErrMsgTxt(bad);
+    float sigma[3];
+    for (size_t j = 0; j < 3; ++j) {
+      const size_t k = n == 1 ? 0 : j;
+      sigma[j] = f32 ? static_cast<const float *>(mxGetData(g))[k] : (float)static_cast<const double *>(mxGetData(g))[k];
+    }
+    check(vr_set_smoothing(h, sigma));
+    return;
+  }
   mexErrMsgTxt(("Unknown command: " + std::string(cmd)).c_str());
 }

@@ -26,6 +26,8 @@ VR_TF_VALUE, VR_TF_DEPTH = 0, 1
 VR_TF_MAX_ENTRIES = 1024
 VR_CLIP_MAX = 6
 VR_LABEL_GAINS_MAX = 256
+VR_SMOOTH_MAX_SIGMA = 6.0
+VR_SMOOTH_MAX_TAPS = 25
 # enum vr_slice_mode, enum vr_slice_source, VR_SLICE_MAX_SAMPLES
 VR_SLICE_MAX, VR_SLICE_MIN, VR_SLICE_SUM = 0, 1, 2
 VR_SLICE_EMISSION, VR_SLICE_ABSORPTION, VR_SLICE_REFLECTION = 0, 1, 2
@@ -108,6 +110,14 @@ class VrError(RuntimeError):
 
 _lib = None
 
+# measurement entries that tools/ bind and include/vrhip.h does not declare (csrc/vr_capi.hip)
+TOOL_SIGNATURES = [
+    ("vr_smooth_axis_device", c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
+    ("vr_smooth_fused_device", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("vr_debug_read_emission", c_int, [c_void_p, c_uint64, c_uint64, c_void_p]),
+    ("vr_debug_derive_times", c_int, [c_void_p, c_void_p]),
+]
+
 # (name, restype, argtypes) for every symbol of include/vrhip.h
 SIGNATURES = [
     ("vr_new", c_int, [POINTER(c_void_p)]),
@@ -146,6 +156,10 @@ SIGNATURES = [
     ("vr_set_label_gains", c_int, [c_void_p, c_void_p, c_int32]),
     ("vr_get_label_gains", c_int, [c_void_p, c_void_p, POINTER(c_int32)]),
     ("vr_label_gain_host", c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_uint64, c_void_p]),
+    ("vr_set_smoothing", c_int, [c_void_p, c_void_p]),
+    ("vr_get_smoothing", c_int, [c_void_p, c_void_p]),
+    ("vr_smooth_weights_host", c_int, [c_float, POINTER(c_int32), c_void_p]),
+    ("vr_smooth_host", c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     ("vr_render_slice", c_int, [c_void_p, POINTER(VrSlice), c_void_p, c_void_p, c_void_p]),
     ("vr_render_slice_device", c_int, [c_void_p, POINTER(VrSlice), c_void_p, c_void_p, c_void_p, c_void_p]),
     ("vr_slice_axis", c_int, [POINTER(c_uint64), c_int32, ctypes.c_double, c_uint64, POINTER(VrSlice)]),
@@ -197,7 +211,7 @@ def lib():
             raise ImportError(f"libvrhip.so not built at {LIB_PATH}: run __graft_entry__.build() "
                               "(make -C volume_renderer_amd/csrc)")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, res, args in SIGNATURES:
+        for name, res, args in SIGNATURES + TOOL_SIGNATURES:
             if LIB_PATH != _DEFAULT_PATH and not hasattr(handle, name):
                 continue  # an A/B build of an earlier tree (VR_LIB_PATH) may predate a diagnostic entry
             fn = getattr(handle, name)

@@ -179,6 +179,8 @@ int vr_delete(vr_context *h) {
     free_labels(h);
     if (h->d_gains) (void)hipFree(h->d_gains);
     h->d_gains = nullptr;
+    if (h->d_smooth_w) (void)hipFree(h->d_smooth_w);
+    h->d_smooth_w = nullptr;
   }
   g_contexts.erase(h);
   h->signature = 0;
@@ -218,8 +220,11 @@ int vr_mem_info(vr_context *h, char *buf, size_t buflen) {
      << "\t\tlight (MB): " << mb(h->vol[T_LIGHT].memory_size) << " ptr: " << ptr(T_LIGHT) << "\n"
      << "\t\tlabels (MB): " << mb(h->labels_bytes) << " ptr: " << (const void *)h->d_labels
      << ", label gains: " << h->ngains << ", unmodified emission copy (MB): "
-     << mb(label_target(h) && label_target(h)->orig ? label_target(h)->bytes : 0) << "\n"
-     << "\t\treusable buffers (MB): " << mb(vr_host::pool_bytes(h->device)) << "\n\n"
+     << mb(label_target(h) && label_target(h)->orig ? label_target(h)->bytes : 0) << "\n";
+  if (smoothing_set(h))  // (only while one is set: without, the report is what it was)
+    os << "\t\tsmoothing sigma (voxels): " << h->smooth_sigma[0] << " " << h->smooth_sigma[1] << " "
+       << h->smooth_sigma[2] << ", derived from the unmodified emission copy above\n";
+  os << "\t\treusable buffers (MB): " << mb(vr_host::pool_bytes(h->device)) << "\n\n"
      << "\t\tSimilarity of Volumes\n\t\t---------------------\n"
      << "\t\t\tEm\tAb\tRe\n"
      << "\t\tEm\t1\t\n"
@@ -702,7 +707,7 @@ int vr_sync_labels(vr_context *h, const vr_volume *labels) {
   if (!count) {  // NULL (or an empty volume) drops them
     if (h->d_labels) h->labels_version = next_version();
     free_labels(h);
-    return apply_labels(h);
+    return apply_derived(h);
   }
   const BufPtr b = label_target(h);
   if (h->ngains > 0)
@@ -721,7 +726,7 @@ int vr_sync_labels(vr_context *h, const vr_volume *labels) {
       h->labels_bytes = count;
     }
     h->labels_readers.wait();  // slices in flight that read the label bytes
-    // (no label pass is in flight: apply_labels waits for its own.)  Device data is read after the work
+    // (no label pass is in flight: apply_derived waits for its own.)  Device data is read after the work
     // already queued on the null stream, as the upload path reads a device volume.
     const bool dev = labels->location == VR_DEVICE;
     VR_HIP(hipMemcpy(h->d_labels, labels->data, count, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
@@ -732,7 +737,7 @@ int vr_sync_labels(vr_context *h, const vr_volume *labels) {
     h->labels_location = labels->location;
     h->labels_version = next_version();
   }
-  return apply_labels(h);
+  return apply_derived(h);
   VR_GUARD_END
 }
 
@@ -754,7 +759,7 @@ int vr_set_label_gains(vr_context *h, const float *gains, int32_t n) {
   for (int32_t i = 0; i < n; ++i) h->gains[i] = gains[i];
   h->ngains = n;
   h->gains_version = next_version();
-  return apply_labels(h);
+  return apply_derived(h);
   VR_GUARD_END
 }
 
@@ -773,6 +778,154 @@ int vr_label_gain_host(const float *src, const uint8_t *labels, const float *gai
   if (count && (!src || !dst || (n > 0 && !labels))) return fail(VR_ERR_ARGUMENT, "label gains: src / labels / dst is NULL");
   for (uint64_t i = 0; i < count; ++i) dst[i] = vr_label_gain(src[i], n > 0 ? labels[i] : 0u, gains, n);
   return VR_OK;
+}
+
+int vr_set_smoothing(vr_context *h, const float sigma[3]) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (int rc = check_smoothing(sigma)) return rc;
+  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
+  const float zero[3] = {0.f, 0.f, 0.f};
+  const float *sg = sigma ? sigma : zero;
+  const bool any = sg[0] != 0.f || sg[1] != 0.f || sg[2] != 0.f;
+  if (any && !h->children.empty()) return smoothing_unsupported("vr_set_smoothing");
+  if (sg[0] == h->smooth_sigma[0] && sg[1] == h->smooth_sigma[1] && sg[2] == h->smooth_sigma[2]) return VR_OK;  // no change
+  VR_GUARD_BEGIN
+  DeviceGuard dg(h->device);
+  vr_host::prune_retired();
+  const float old[3] = {h->smooth_sigma[0], h->smooth_sigma[1], h->smooth_sigma[2]};
+  const uint64_t old_version = h->smooth_version;
+  for (int j = 0; j < 3; ++j) h->smooth_sigma[j] = sg[j] + 0.f;  // (-0 is no smoothing)
+  h->smooth_version = next_version();
+  int rc = VR_OK;
+  try {
+    rc = apply_derived(h);
+  } catch (...) {  // a failed pass left the unmodified upload: the handle says so (no sigma), and the same
+    for (int j = 0; j < 3; ++j) h->smooth_sigma[j] = 0.f;  // sigma set again is a change and derives again
+    h->smooth_version = next_version();
+    throw;
+  }
+  if (rc == VR_ERR_VRAM) {  // nothing was written: the state stays as it was
+    for (int j = 0; j < 3; ++j) h->smooth_sigma[j] = old[j];
+    h->smooth_version = old_version;
+  }
+  return rc;
+  VR_GUARD_END
+}
+
+int vr_get_smoothing(vr_context *h, float sigma[3]) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!sigma) return fail(VR_ERR_ARGUMENT, "smoothing: sigma is NULL");
+  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
+  for (int j = 0; j < 3; ++j) sigma[j] = h->smooth_sigma[j];
+  return VR_OK;
+}
+
+int vr_smooth_weights_host(float sigma, int32_t *radius, float *w) {
+  const float s3[3] = {sigma, 0.f, 0.f};
+  if (int rc = check_smoothing(s3)) return rc;
+  if (!radius || !w) return fail(VR_ERR_ARGUMENT, "smoothing: radius / w is NULL");
+  *radius = vr_smooth_weights(sigma, w);
+  return VR_OK;
+}
+
+int vr_smooth_host(const float *src, const uint64_t dims[3], const float sigma[3], float *dst) {
+  if (int rc = check_smoothing(sigma)) return rc;
+  if (!dims || !sigma) return fail(VR_ERR_ARGUMENT, "smoothing: dims / sigma is NULL");
+  if (dims[0] > 0x7FFFFFFF || dims[1] > 0x7FFFFFFF || dims[2] > 0x7FFFFFFF)
+    return fail(VR_ERR_UNSUPPORTED, "smoothing: volume dimension too large");
+  const uint64_t count = dims[0] * dims[1] * dims[2];
+  if (!count) return VR_OK;
+  if (!src || !dst) return fail(VR_ERR_ARGUMENT, "smoothing: src / dst is NULL");
+  try {
+    int axes[3], np = 0;
+    for (int j = 0; j < 3; ++j)
+      if (sigma[j] > 0.f && dims[j] > 1) axes[np++] = j;
+    if (!np) {
+      if (dst != src) std::memcpy(dst, src, count * sizeof(float));
+      return VR_OK;
+    }
+    // the passes alternate between dst and one temporary so that the last writes dst; a first pass
+    // that would write the array it reads (dst == src) reads a copy
+    std::vector<float> tmp(np > 1 ? count : 0), copy;
+    const float *in = src;
+    if (np % 2 == 1 && dst == src) {
+      copy.assign(src, src + count);
+      in = copy.data();
+    }
+    for (int i = 0; i < np; ++i) {
+      const int j = axes[i];
+      float w[VR_SMOOTH_MAX_TAPS];
+      const int32_t R = vr_smooth_weights(sigma[j], w);
+      float *out = (np - 1 - i) % 2 ? tmp.data() : dst;
+      const int64_t n = (int64_t)dims[j];
+      const uint64_t stride = j == 0 ? 1 : (j == 1 ? dims[0] : dims[0] * dims[1]);
+      const uint64_t inner = stride, outer = count / (stride * dims[j]);
+      for (uint64_t o = 0; o < outer; ++o)
+        for (int64_t c = 0; c < n; ++c)
+          for (uint64_t q = 0; q < inner; ++q) {
+            const uint64_t base = o * stride * dims[j] + q;
+            out[base + (uint64_t)c * stride] = vr_smooth_tap(w, R, [=](int32_t k) {
+              int64_t t = c - R + k;
+              t = t < 0 ? 0 : (t > n - 1 ? n - 1 : t);
+              return in[base + (uint64_t)t * stride];
+            });
+          }
+      in = out;
+    }
+  } catch (const std::bad_alloc &) {
+    return fail(VR_ERR_DEVICE, "host out of memory");
+  }
+  return VR_OK;
+}
+
+// Measurement entries of tools/smooth_bench.py, not part of include/vrhip.h: one axis pass, or the fused
+// launch, between two padded device buffers (d_weights: 3 x 25 floats for the fused form, 2 radius + 1 for
+// a pass), and a read-back of `count` floats at element `offset` of the handle's resident emission buffer.
+extern "C" int vr_smooth_axis_device(const float *d_src, float *d_dst, const uint64_t dims[3], int32_t axis,
+                                     const float *d_weights, int32_t radius, void *d_stats, void *stream) {
+  if (!d_src || !d_dst || d_src == d_dst || !dims || !d_weights || axis < 0 || axis > 2 || radius < 1 ||
+      radius > VR_SMOOTH_MAX_RADIUS || !dims[0] || !dims[1] || !dims[2] || dims[0] > 0x7FFFFFFF ||
+      dims[1] > 0x7FFFFFFF || dims[2] > 0x7FFFFFFF)
+    return fail(VR_ERR_ARGUMENT, "smoothing: invalid pass arguments");
+  VR_GUARD_BEGIN
+  VR_HIP(vr::launch_smooth_axis(d_src, d_dst, (int32_t)dims[0], (int32_t)dims[1], (int32_t)dims[2], axis, d_weights,
+                                radius, static_cast<vr::BufStats *>(d_stats), (hipStream_t)stream));
+  return VR_OK;
+  VR_GUARD_END
+}
+
+extern "C" int vr_smooth_fused_device(const float *d_src, float *d_dst, const uint64_t dims[3], const float *d_weights,
+                                      const int32_t radius[3], void *d_stats, void *stream) {
+  if (!d_src || !d_dst || d_src == d_dst || !dims || !d_weights || !radius || dims[0] > 0x7FFFFFFF ||
+      dims[1] > 0x7FFFFFFF || dims[2] > 0x7FFFFFFF)
+    return fail(VR_ERR_ARGUMENT, "smoothing: invalid pass arguments");
+  VR_GUARD_BEGIN
+  VR_HIP(vr::launch_smooth_fused(d_src, d_dst, (int32_t)dims[0], (int32_t)dims[1], (int32_t)dims[2], d_weights,
+                                 radius[0], radius[1], radius[2], static_cast<vr::BufStats *>(d_stats),
+                                 (hipStream_t)stream));
+  return VR_OK;
+  VR_GUARD_END
+}
+
+extern "C" int vr_debug_derive_times(vr_context *h, double out[2]) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!valid(h) || !out) return fail(VR_ERR_HANDLE, "Handle not valid.");
+  out[0] = h->derive_ms[0];
+  out[1] = h->derive_ms[1];
+  return VR_OK;
+}
+
+extern "C" int vr_debug_read_emission(vr_context *h, uint64_t offset, uint64_t count, float *out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
+  const BufPtr b = label_target(h);
+  if (!b || !b->ptr || !out || offset + count > b->bytes / sizeof(float))
+    return fail(VR_ERR_ARGUMENT, "read_emission: no resident emission buffer, or a range outside it");
+  VR_GUARD_BEGIN
+  DeviceGuard dg(h->device);
+  VR_HIP(hipMemcpy(out, b->ptr + offset, count * sizeof(float), hipMemcpyDeviceToHost));
+  return VR_OK;
+  VR_GUARD_END
 }
 
 int vr_clip_convert_host(const vr_clip_plane *planes, int32_t n, const float bmin[3], const float bscale[3],
@@ -815,6 +968,7 @@ int vr_render_slab(vr_context *h, const vr_render_args *a, const vr_slab *slab, 
   if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
   if (!a) return fail(VR_ERR_ARGUMENT, "insufficient parameter!");
   if (h->nclip) return clip_unsupported("vr_render_slab");
+  if (smoothing_set(h)) return smoothing_unsupported("vr_render_slab");
   VR_GUARD_BEGIN
   DeviceGuard dg(h->device);
   vr_host::prune_retired();  // buffers whose last launch has completed

@@ -2,7 +2,7 @@
 // handle and the module state's types, the checked-call and entry-guard macros, the tuning constants,
 // the shared state (vr_state.hip) and the functions that cross files, all in namespace vr_host.
 //   vr_state.hip     the shared state, the switches, the stream pool, the kernel files' callbacks
-//   vr_sync.hip      upload and slot state machine, memory checks, label gains, do_sync_volumes
+//   vr_sync.hip      upload and slot state machine, memory checks, smoothing and label gains, do_sync_volumes
 //   vr_frame.hip     clip conversion, build_frame, lights, partition, depth lanes, the march entry table, schedules
 //   vr_render.hip    do_render, do_render_slab, the multi-device group, view sets / channels
 //   vr_features.hip  projection, slice, isosurface and transfer renders, the volume histogram
@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include <array>
+#include <chrono>
 #include <cmath>
 #include <set>
 #include <sstream>
@@ -23,6 +24,7 @@
 #include "vr_launch.h"
 #include "vr_resources.h"
 #include "vr_slice.h"
+#include "vr_smooth.h"
 
 #ifndef VR_DEPTH_ROUNDS_K1
 #define VR_DEPTH_ROUNDS_K1 16.0  // K = 1 needs >= this many K = 1 waves per device wave slot (and sparse sampling)
@@ -135,10 +137,12 @@ struct DevBuf {
   // unmodified padded upload (`bytes` long) with its statistics, and ptr, nonfinite, maxabs and occ
   // are those of the modulated values; mod_labels / mod_gains name the label upload and the gain
   // table that ptr was derived from.  Only the label pass reads orig, and the host waits for it.
+  // Smoothing (vr_set_smoothing) shares the copy: ptr is orig smoothed, then modulated;
+  // mod_smooth names the sigma it was smoothed with (0: not smoothed).
   float *orig = nullptr;
   bool orig_nonfinite = false;
   float orig_maxabs = 0.f;
-  uint64_t mod_labels = 0, mod_gains = 0;
+  uint64_t mod_labels = 0, mod_gains = 0, mod_smooth = 0;
   ~DevBuf() {
     if (orig) vr_host::pooled_free(orig, bytes, device, vr_host::Readers());
     if (zpair) vr_host::pooled_free(zpair, zpair_bytes, device, vr_host::Readers(readers));
@@ -234,6 +238,15 @@ struct vr_context {
   // slices in flight that read d_labels (vr_render_slice_device's label plane): the label bytes are
   // neither overwritten nor freed before all of them have completed
   vr_host::Readers labels_readers;
+  // Gaussian smoothing (vr_set_smoothing): sigma per axis of Data as the caller gave it
+  // (all zero: none), the version that keys DevBuf::mod_smooth, and the device copy of the three axes'
+  // weights (VR_SMOOTH_MAX_TAPS floats each)
+  float smooth_sigma[3] = {0.f, 0.f, 0.f};
+  uint64_t smooth_version = 0;
+  float *d_smooth_w = nullptr;
+  // the last derivation's host-clock times (ms), each ending in a stream synchronise: the passes with the
+  // statistics read-back, the occupancy rebuild (tools/smooth_bench.py reads them)
+  double derive_ms[2] = {0.0, 0.0};
 };
 
 namespace vr_host {
@@ -352,7 +365,10 @@ uint64_t required_memory(const vr_context *h);
 int check_free_device_memory(uint64_t required);
 BufPtr label_target(const vr_context *h);
 int check_label_dims(const uint64_t ld[3], const DevBuf *b);
-int apply_labels(vr_context *h);
+int apply_derived(vr_context *h);
+bool smoothing_set(const vr_context *h);
+int check_smoothing(const float sigma[3]);
+int smoothing_unsupported(const char *what);
 void free_labels(vr_context *h);
 int labels_unsupported(const char *what);
 int check_label_gains(const float *gains, int32_t n);

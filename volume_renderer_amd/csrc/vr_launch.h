@@ -75,6 +75,13 @@ hipError_t launch_histogram_finalize(const unsigned long long *counts, const voi
 // vr_labels.hip: dst = src under the n gains of `gains` by the dense label bytes; *st += the statistics of dst
 hipError_t launch_label_gain(const float *src, const uint8_t *labels, const float *gains, int32_t n, int32_t nx,
                              int32_t ny, int32_t nz, float *dst, BufStats *st, hipStream_t s);
+// vr_smooth.hip: one axis (0 / 1 / 2 along dims[0] / [1] / [2]) of the Gaussian smoothing, src -> dst, both
+// padded; wts: the 2R+1 weights in device memory; st null, or *st += the statistics of dst
+hipError_t launch_smooth_axis(const float *src, float *dst, int32_t nx, int32_t ny, int32_t nz, int axis,
+                              const float *wts, int32_t R, BufStats *st, hipStream_t s);
+// vr_smooth.hip: the three axes in one launch (every dim >= 2, every radius >= 1); wts: 3 x 25 weights
+hipError_t launch_smooth_fused(const float *src, float *dst, int32_t nx, int32_t ny, int32_t nz, const float *wts,
+                               int32_t Rx, int32_t Ry, int32_t Rz, BufStats *st, hipStream_t s);
 hipError_t launch_predict_cost(const RenderParams &P, uint32_t nb_view, uint32_t nbx, int32_t tw, int32_t th,
                                int32_t m, float dens, float xthr, uint32_t *cost, hipStream_t s);
 uint64_t interleave3_entries(uint32_t px, uint32_t py, uint32_t pz);

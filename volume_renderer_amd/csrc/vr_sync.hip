@@ -5,7 +5,7 @@
 //     re-expressed as host state: "textures" are bindings of device buffers (fp32 volumes resident in HBM,
 //     read by the software sampler of vr_kernels.hip), the slot indices d_idx* stay module-global exactly
 //     as in the reference
-//   - label gains
+//   - Gaussian smoothing and label gains, one derivation from the unmodified upload
 #include "vr_host.h"
 
 namespace vr_host {
@@ -104,11 +104,11 @@ static void build_occupancy(DevBuf *b, hipStream_t s) {
   VR_HIP(hipStreamSynchronize(s));
 }
 
-// Forget that b was modulated by label gains: its unmodified copy goes back to the pool (no launch reads it).
+// Forget that b was smoothed or modulated by label gains: its unmodified copy goes back to the pool (no launch reads it).
 static void drop_unmodified_copy(DevBuf *b) {
   if (b->orig) vr_host::pooled_free(b->orig, b->bytes, b->device, vr_host::Readers());
   b->orig = nullptr;
-  b->mod_labels = b->mod_gains = 0;
+  b->mod_labels = b->mod_gains = b->mod_smooth = 0;
 }
 
 static void sync_volume(vr_context *h, int tex, int slot) {
@@ -124,7 +124,7 @@ static void sync_volume(vr_context *h, int tex, int slot) {
     b->bytes = padded;
     if (padded) VR_HIP(vr_host::pooled_alloc(reinterpret_cast<void **>(&b->ptr), padded, h->device));
   }
-  drop_unmodified_copy(b.get());  // (the upload overwrites the modulated values: apply_labels starts afresh)
+  drop_unmodified_copy(b.get());  // (the upload overwrites the derived values: apply_derived starts afresh)
   for (int i = 0; i < 3; ++i) b->dims[i] = v.dims[i];
   b->nonfinite = false;
   b->maxabs = 0.f;
@@ -192,7 +192,8 @@ uint64_t required_memory(const vr_context *h) {
   r += h->vol[T_DX].memory_size + h->vol[T_DY].memory_size + h->vol[T_DZ].memory_size;
   // label gains: the label bytes, and the unmodified copy of the emission volume while gains are set
   r += h->labels_bytes;
-  if (h->d_labels && h->ngains > 0) r += em.memory_size;
+  // (one copy, shared with the smoothing while a sigma is set)
+  if ((h->d_labels && h->ngains > 0) || smoothing_set(h)) r += em.memory_size;
   return r;
 }
 
@@ -275,30 +276,100 @@ static void restore_unmodified(DevBuf *b) {
   b->orig = nullptr;
   b->nonfinite = b->orig_nonfinite;
   b->maxabs = b->orig_maxabs;
-  b->mod_labels = b->mod_gains = 0;
+  b->mod_labels = b->mod_gains = b->mod_smooth = 0;
   b->version = next_version();
   build_occupancy(b, label_uploader(b->device).pad_stream);
 }
 
-// Bring the handle's emission buffer up to date with its labels and gains: modulated when emission,
-// labels and n > 0 are all present, unmodified otherwise; nothing is written when nothing changed.
-// The first modulation of an upload takes a second buffer and swaps: the upload becomes the
-// unmodified copy, the pass writes the new ptr (no copy of the volume).  The state left is that of an
-// upload of the host-rewritten volume: data and apron, statistics, occupancy map, a new version.
-int apply_labels(vr_context *h) {
+// ---- Gaussian smoothing (include/vrhip.h vr_set_smoothing) ----------------------------
+bool smoothing_set(const vr_context *h) {
+  return h->smooth_sigma[0] != 0.f || h->smooth_sigma[1] != 0.f || h->smooth_sigma[2] != 0.f;
+}
+
+int check_smoothing(const float sigma[3]) {
+  if (!sigma) return VR_OK;
+  for (int j = 0; j < 3; ++j) {
+    if (!(sigma[j] >= 0.f) || !std::isfinite(sigma[j]))
+      return fail(VR_ERR_ARGUMENT, "smoothing: every sigma must be finite and not negative");
+    if (sigma[j] > VR_SMOOTH_MAX_SIGMA) return fail(VR_ERR_ARGUMENT, "smoothing: sigma must be at most 6 voxels");
+  }
+  return VR_OK;
+}
+
+int smoothing_unsupported(const char *what) {
+  return fail(VR_ERR_UNSUPPORTED, std::string(what) + ": Gaussian smoothing (vr_set_smoothing) is not supported " +
+                                      (std::strcmp(what, "vr_render_slab") ? "on a multi-device group handle"
+                                                                           : "by a slab render: a slab's z border "
+                                                                             "would be clamped"));
+}
+
+// Which form of the smoothing kernels serves three active axes: the fused launch reads
+// each voxel about once and keeps a ring of 2Rz+1 tile planes in LDS, the three passes move the volume
+// three times.  Measured at 1024^3, both forms interleaved (profiles/round22/smooth.json): the fused call
+// takes 1.03 (V_shell) / 1.00 (random) times the passes' at sigma 1, 1.77 / 1.64 times at sigma 2 and
+// 7.2 / 6.7 times at sigma 6 -- its halo recomputation and four barriers per plane cost more than the
+// bytes it saves -- so the passes serve every radius and the fused form runs only when forced.
+// VR_SMOOTH_FORM=fused|passes (test switch) forces either side; both give the same bits.
+#ifndef VR_SMOOTH_FUSED_MAX_R
+#define VR_SMOOTH_FUSED_MAX_R 0  // fused up to this largest radius of the three axes; 0: never
+#endif
+static bool smooth_fused(int32_t Rx, int32_t Ry, int32_t Rz) {
+  if (const char *ev = test_env("VR_SMOOTH_FORM")) {
+    if (ev[0] == 'f') return true;
+    if (ev[0] == 'p') return false;
+  }
+  return std::max(Rx, std::max(Ry, Rz)) <= VR_SMOOTH_FUSED_MAX_R;
+}
+
+// Bring the handle's emission buffer up to date with its smoothing, labels and gains, one derivation
+// from the unmodified upload: orig -> smoothing (one pass per axis with sigma > 0 and more than one
+// voxel, dims[0] first) -> label gains (when emission, labels and n > 0 are all present) -> ptr;
+// unmodified when no pass is left; nothing is written when nothing changed.
+// The first derivation of an upload takes a second buffer and swaps: the upload becomes the unmodified
+// copy, the last pass writes the new ptr (no copy of the volume).  Passes in between alternate between
+// ptr and one scratch volume from the pool, which goes back afterwards.  The statistics fold into the
+// last pass.  The state left is that of an upload of the host-rewritten volume: data and apron,
+// statistics, occupancy map, a new version.  VR_ERR_VRAM (nothing changed) when the copy and the
+// scratch volume do not fit.
+int apply_derived(vr_context *h) {
   BufPtr b = label_target(h);
   if (!b || !b->ptr) return VR_OK;
-  const bool want = h->d_labels && h->ngains > 0;
-  const int bad = want ? check_label_dims(h->labels_dims, b.get()) : VR_OK;
-  if (!want || bad) {
+  bool gain = h->d_labels && h->ngains > 0;
+  const int bad = gain ? check_label_dims(h->labels_dims, b.get()) : VR_OK;
+  if (bad) gain = false;
+  struct Pass {
+    int axis;  // 0..2 a smoothing axis, 3 the gains, 4 the three axes fused
+    int32_t R;
+  } pass[4];
+  int32_t radius[3] = {0, 0, 0};
+  int np = 0;
+  float wts[3 * VR_SMOOTH_MAX_TAPS] = {};
+  for (int j = 0; j < 3; ++j)
+    if (h->smooth_sigma[j] > 0.f && b->dims[j] > 1)
+      pass[np++] = Pass{j, radius[j] = vr_smooth_weights(h->smooth_sigma[j], wts + j * VR_SMOOTH_MAX_TAPS)};
+  const bool smooth = np > 0;
+  if (np == 3 && smooth_fused(pass[0].R, pass[1].R, pass[2].R)) {  // the three axes in one launch
+    pass[0].axis = 4;
+    np = 1;
+  }
+  if (gain) pass[np++] = Pass{3, 0};
+  if (!np) {
     restore_unmodified(b.get());
     return bad;
   }
-  if (b->orig && b->mod_labels == h->labels_version && b->mod_gains == h->gains_version) return VR_OK;
+  const uint64_t kl = gain ? h->labels_version : 0, kg = gain ? h->gains_version : 0,
+                 ks = smooth ? h->smooth_version : 0;
+  if (b->orig && b->mod_labels == kl && b->mod_gains == kg && b->mod_smooth == ks) return bad;
+  if (smooth) {  // (the gain pass alone was checked by its caller, as before)
+    const uint64_t need = (b->orig ? 0 : b->bytes) + (np > 1 ? b->bytes : 0);
+    if (int rc = check_free_device_memory(need)) return rc;
+  }
   vr_host::Uploader &U = label_uploader(b->device);
-  if (!h->d_gains)
+  if (gain && !h->d_gains)
     VR_HIP(vr_host::device_alloc(reinterpret_cast<void **>(&h->d_gains), sizeof(h->gains)));
-  b->readers.wait();  // "neither rewritten nor freed before all of them": renders in flight keep their gains
+  if (smooth && !h->d_smooth_w)
+    VR_HIP(vr_host::device_alloc(reinterpret_cast<void **>(&h->d_smooth_w), sizeof(wts)));
+  b->readers.wait();  // "neither rewritten nor freed before all of them": renders in flight keep their volume
   if (!b->orig) {
     float *fresh = nullptr;
     VR_HIP(vr_host::pooled_alloc(reinterpret_cast<void **>(&fresh), b->bytes, b->device));
@@ -307,19 +378,44 @@ int apply_labels(vr_context *h) {
     b->orig_nonfinite = b->nonfinite;
     b->orig_maxabs = b->maxabs;
   }
-  b->mod_labels = b->mod_gains = 0;  // (until the pass below has completed)
+  b->mod_labels = b->mod_gains = b->mod_smooth = 0;  // (until the passes below have completed)
+  float *scratch = nullptr;
   try {
-    VR_HIP(hipMemcpy(h->d_gains, h->gains, sizeof(float) * (size_t)h->ngains, hipMemcpyHostToDevice));
+    if (np > 1) VR_HIP(vr_host::pooled_alloc(reinterpret_cast<void **>(&scratch), b->bytes, b->device));
+    if (gain) VR_HIP(hipMemcpy(h->d_gains, h->gains, sizeof(float) * (size_t)h->ngains, hipMemcpyHostToDevice));
+    if (smooth) VR_HIP(hipMemcpy(h->d_smooth_w, wts, sizeof(wts), hipMemcpyHostToDevice));
     VR_HIP(hipMemsetAsync(U.d_stats, 0, sizeof(vr::BufStats), U.pad_stream));
-    VR_HIP(vr::launch_label_gain(b->orig, h->d_labels, h->d_gains, h->ngains, (int32_t)b->dims[0], (int32_t)b->dims[1],
-                                 (int32_t)b->dims[2], b->ptr, U.d_stats, U.pad_stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    const int32_t nx = (int32_t)b->dims[0], ny = (int32_t)b->dims[1], nz = (int32_t)b->dims[2];
+    const float *src = b->orig;
+    for (int i = 0; i < np; ++i) {
+      float *dst = (np - 1 - i) % 2 ? scratch : b->ptr;  // the last pass writes ptr
+      vr::BufStats *st = i == np - 1 ? U.d_stats : nullptr;
+      if (pass[i].axis == 4)
+        VR_HIP(vr::launch_smooth_fused(src, dst, nx, ny, nz, h->d_smooth_w, radius[0], radius[1], radius[2], st,
+                                       U.pad_stream));
+      else if (pass[i].axis == 3)
+        VR_HIP(vr::launch_label_gain(src, h->d_labels, h->d_gains, h->ngains, nx, ny, nz, dst, st, U.pad_stream));
+      else
+        VR_HIP(vr::launch_smooth_axis(src, dst, nx, ny, nz, pass[i].axis,
+                                      h->d_smooth_w + pass[i].axis * VR_SMOOTH_MAX_TAPS, pass[i].R, st, U.pad_stream));
+      src = dst;
+    }
     VR_HIP(hipMemcpyAsync(U.h_stats, U.d_stats, sizeof(vr::BufStats), hipMemcpyDeviceToHost, U.pad_stream));
     VR_HIP(hipStreamSynchronize(U.pad_stream));
+    if (scratch) vr_host::pooled_free(scratch, b->bytes, b->device, vr_host::Readers());
+    scratch = nullptr;
     b->nonfinite = U.h_stats->nonfinite != 0;
     b->maxabs = U.h_stats->maxabs;
     b->version = next_version();
+    const auto t1 = std::chrono::steady_clock::now();
     build_occupancy(b.get(), U.pad_stream);
+    const auto t2 = std::chrono::steady_clock::now();
+    h->derive_ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    h->derive_ms[1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
   } catch (...) {  // the buffer must not stay half written: back to the unmodified upload
+    (void)hipStreamSynchronize(U.pad_stream);
+    if (scratch) vr_host::pooled_free(scratch, b->bytes, b->device, vr_host::Readers());
     vr_host::pooled_free(b->ptr, b->bytes, b->device, vr_host::Readers());
     b->ptr = b->orig;
     b->orig = nullptr;
@@ -328,9 +424,10 @@ int apply_labels(vr_context *h) {
     b->version = next_version();
     throw;
   }
-  b->mod_labels = h->labels_version;
-  b->mod_gains = h->gains_version;
-  return VR_OK;
+  b->mod_labels = kl;
+  b->mod_gains = kg;
+  b->mod_smooth = ks;
+  return bad;
 }
 
 void free_labels(vr_context *h) {
@@ -405,7 +502,7 @@ int do_sync_volumes(vr_context *h, uint64_t time_last_mem_sync, const vr_volume 
   h->snap_idx[2] = g_tex.idx_re;
   h->snap_grad = g_tex.grad_method;
   h->has_snap = true;
-  return apply_labels(h);  // label gains: the freshly bound emission buffer follows the handle's table
+  return apply_derived(h);  // smoothing, label gains: the freshly bound emission buffer follows the handle's state
   VR_GUARD_END
 }
 

@@ -524,6 +524,93 @@ def label_gain_host(src, labels, gains) -> np.ndarray:
     return out.reshape(s.shape, order="F")
 
 
+def smoothing_sigma(sigma):
+    """A smoothing sigma as three singles along dims[0..2] of Data: a real scalar (all three axes) or a
+    3-vector; None, False or empty: none (all zero).  The library checks the values."""
+    if sigma is None or _is_false(sigma):
+        return np.zeros(3, np.float32)
+    a = np.asarray(sigma)
+    if a.size == 0:
+        return np.zeros(3, np.float32)
+    if a.dtype.kind not in "fiu" or a.size not in (1, 3) or a.size != max(a.shape, default=1):
+        raise _lib.VrError(1, "set_smoothing: sigma must be a real scalar or 3-vector, [] or false")
+    a = a.reshape(-1).astype(np.float32)
+    return np.ascontiguousarray(np.repeat(a, 3) if a.size == 1 else a)
+
+
+def set_smoothing(handle, sigma) -> None:
+    """vr_set_smoothing: Gaussian smoothing of the handle's resident emission volume, sigma in voxels
+    (smoothing_sigma(); None / False / [] / zeros clear it)."""
+    a = smoothing_sigma(sigma)
+    check(lib().vr_set_smoothing(_handle(handle), a.ctypes.data))
+
+
+def get_smoothing(handle) -> np.ndarray:
+    """vr_get_smoothing: the handle's sigma as set, [3] single (zeros: none)."""
+    out = np.zeros(3, np.float32)
+    check(lib().vr_get_smoothing(_handle(handle), out.ctypes.data))
+    return out
+
+
+def smooth_weights_host(sigma):
+    """vr_smooth_weights_host: (R, the 2R+1 fp32 weights) of one axis."""
+    w = np.zeros(_lib.VR_SMOOTH_MAX_TAPS, np.float32)
+    r = ctypes.c_int32(0)
+    check(lib().vr_smooth_weights_host(float(np.float32(sigma)), ctypes.byref(r), w.ctypes.data))
+    return int(r.value), w[:2 * r.value + 1].copy()
+
+
+def smooth_host(src, sigma) -> np.ndarray:
+    """vr_smooth_host: the smoothing's value rule on the CPU -- src single with at most 3 dimensions
+    (column-major: axis j of the array is dims[j]), sigma as smoothing_sigma(); shaped like src."""
+    s = np.asarray(src, dtype=np.float32)
+    if s.ndim > 3:
+        raise _lib.VrError(1, "smooth_host: src must have at most 3 dimensions")
+    dims = (ctypes.c_uint64 * 3)(*(list(s.shape) + [1] * (3 - s.ndim)))
+    sf = np.ascontiguousarray(s.reshape(-1, order="F"))
+    a = smoothing_sigma(sigma)
+    out = np.empty(sf.size, np.float32)
+    check(lib().vr_smooth_host(sf.ctypes.data, dims, a.ctypes.data, out.ctypes.data))
+    return out.reshape(s.shape, order="F")
+
+
+def smooth_fused_device(d_src: int, d_dst: int, dims, d_weights: int, radius, d_stats: int = 0, stream: int = 0) -> None:
+    """vr_smooth_fused_device: the fused launch between two padded device buffers (measurements); d_weights
+    3 x 25 floats, radius three ints."""
+    d = (ctypes.c_uint64 * 3)(*(int(x) for x in dims))
+    r = (ctypes.c_int32 * 3)(*(int(x) for x in radius))
+    check(lib().vr_smooth_fused_device(ctypes.c_void_p(int(d_src)), ctypes.c_void_p(int(d_dst)), d,
+                                       ctypes.c_void_p(int(d_weights)), r,
+                                       ctypes.c_void_p(int(d_stats)) if d_stats else None,
+                                       ctypes.c_void_p(int(stream)) if stream else None))
+
+
+def read_emission(handle, offset: int, count: int) -> np.ndarray:
+    """vr_debug_read_emission: `count` floats at element `offset` of the handle's padded resident emission
+    buffer (measurements)."""
+    out = np.empty(int(count), np.float32)
+    check(lib().vr_debug_read_emission(_handle(handle), int(offset), int(count), out.ctypes.data))
+    return out
+
+
+def derive_times(handle):
+    """vr_debug_derive_times: (ms of the last derivation's passes with the statistics read-back, ms of its
+    occupancy rebuild), host clock (measurements)."""
+    out = (ctypes.c_double * 2)()
+    check(lib().vr_debug_derive_times(_handle(handle), out))
+    return float(out[0]), float(out[1])
+
+
+def smooth_axis_device(d_src: int, d_dst: int, dims, axis: int, d_weights: int, radius: int, d_stats: int = 0,
+                       stream: int = 0) -> None:
+    """vr_smooth_axis_device: one axis pass between two padded device buffers (measurements)."""
+    d = (ctypes.c_uint64 * 3)(*(int(x) for x in dims))
+    check(lib().vr_smooth_axis_device(ctypes.c_void_p(int(d_src)), ctypes.c_void_p(int(d_dst)), d, int(axis),
+                                      ctypes.c_void_p(int(d_weights)), int(radius),
+                                      ctypes.c_void_p(int(d_stats)) if d_stats else None,
+                                      ctypes.c_void_p(int(stream)) if stream else None))
+
+
 SLICE_MODES = {"max": _lib.VR_SLICE_MAX, "min": _lib.VR_SLICE_MIN, "sum": _lib.VR_SLICE_SUM}
 SLICE_SOURCES = {"emission": _lib.VR_SLICE_EMISSION, "absorption": _lib.VR_SLICE_ABSORPTION,
                  "reflection": _lib.VR_SLICE_REFLECTION}
@@ -815,7 +902,7 @@ def _group_devices():
 def volumeRender(cmd, *args):
     """The `volumeRender` mex: commands 'new', 'delete', 'mem_info', 'sync_volumes', 'render' (and
     'render_stereo', 'render_channels', 'render_projection', 'render_isosurface', 'render_transfer',
-    'render_slice', 'volume_histogram', 'set_clip', 'sync_labels', 'set_label_gains', which the reference does
+    'render_slice', 'volume_histogram', 'set_clip', 'sync_labels', 'set_label_gains', 'set_smoothing', which the reference does
     not have)."""
     nrhs = 1 + len(args)
     if not isinstance(cmd, str) or len(cmd) >= 64:
@@ -899,6 +986,19 @@ def volumeRender(cmd, *args):
             if g.size > _lib.VR_LABEL_GAINS_MAX:
                 raise _lib.VrError(1, "set_label_gains: gains must be a single vector of at most 256 entries, [] or false")
         set_label_gains(args[0], g)
+        return None
+    if cmd == "set_smoothing":  # ('set_smoothing', h, sigma): a single or double scalar or 3-vector; [] / false clears
+        if nrhs < 3:
+            raise _lib.VrError(1, "insufficient parameter!")
+        if nrhs > 3:
+            raise _lib.VrError(1, "set_smoothing: too many input arguments")
+        sg = args[1]
+        if not (sg is None or _is_false(sg)):
+            sg = np.asarray(sg)
+            if sg.dtype not in (np.float32, np.float64) or sg.ndim > 2 or (sg.size and (
+                    sg.size not in (1, 3) or sg.size != max(sg.shape, default=1))):
+                raise _lib.VrError(1, "set_smoothing: sigma must be a single or double scalar or 3-vector, [] or false")
+        set_smoothing(args[0], sg)
         return None
     if cmd == "render_stereo":  # fused stereo pair (vr_render_stereo): args as 'render' + base
         ra, keep = render_args(*args[1:10])

@@ -95,6 +95,12 @@ class VolumeRender:
         self.LabelGains = np.zeros(0, dtype=np.float32)
         object.__setattr__(self, "_labels_applied", None)  # what the handle holds: None, no labels
         object.__setattr__(self, "_gains_applied", np.zeros(0, dtype=np.float32))
+        # Gaussian smoothing (vr_set_smoothing): sigma in voxels along the three dimensions of
+        # VolumeEmission.Data, a scalar for all three; zeros: none -- the emission volume on the device is
+        # the smoothed Data (times the label gains), without another upload.  Sent to the handle before a
+        # render whenever it differs from what the handle holds (_apply_labels).
+        self.Smoothing = np.zeros(3, dtype=np.float32)
+        object.__setattr__(self, "_smoothing_applied", np.zeros(3, dtype=np.float32))
         if VolumeRender._default_reflection is None:
             VolumeRender._default_reflection = Volume(1)
         # observable properties: defaults are assigned without firing the listener
@@ -156,6 +162,14 @@ class VolumeRender:
             if val.size != max(val.shape, default=0) or val.size > 256:
                 raise TypeError("LabelGains must be a vector of at most 256 gains")
             val = val.reshape(-1).copy()
+        elif name == "Smoothing":
+            val = np.zeros(3, np.float32) if val is None or _is_logical(val) and not val else np.asarray(val)
+            if val.size == 0:
+                val = np.zeros(3, np.float32)
+            if val.dtype.kind not in "fiu" or val.size not in (1, 3) or val.size != max(val.shape, default=1):
+                raise TypeError("Smoothing must be a sigma in voxels: a scalar or a 3-vector")
+            val = val.reshape(-1).astype(np.float32)
+            val = np.repeat(val, 3) if val.size == 1 else val.copy()
         object.__setattr__(self, name, val)
         if name in _VOLUME_PROPS and isinstance(val, Volume):
             val.TimeLastUpdate = timestamp()
@@ -191,7 +205,11 @@ class VolumeRender:
 
     def _apply_labels(self) -> None:
         """'sync_labels' if VolumeLabels changed since the last one (assigned, or a Volume's
-        TimeLastUpdate moved), 'set_label_gains' if LabelGains differs from what the handle holds."""
+        TimeLastUpdate moved), 'set_label_gains' if LabelGains differs from what the handle holds; before
+        them 'set_smoothing' if Smoothing differs from what the handle holds."""
+        if not np.array_equal(self.Smoothing, self._smoothing_applied):
+            volumeRender("set_smoothing", self.objectHandle, self.Smoothing)
+            object.__setattr__(self, "_smoothing_applied", self.Smoothing.copy())
         lb = self.VolumeLabels
         key = None if lb is False else (id(lb), int(lb.TimeLastUpdate) if hasattr(lb, "TimeLastUpdate") else None)
         if key != self._labels_applied:
