@@ -536,6 +536,68 @@ int vr_get_smoothing(vr_context *h, float sigma[3]);
 int vr_smooth_weights_host(float sigma, int32_t *radius, float *w /* room for 25 */);
 int vr_smooth_host(const float *src, const uint64_t dims[3], const float sigma[3], float *dst);
 
+/* --- Richardson-Lucy deconvolution of the resident emission volume (no reference counterpart; on the host
+ * it is deconvlucy(Data, psf, n) with a Gaussian PSF whose axial sigma exceeds the lateral one, and a full
+ * re-upload) ---------------------------------------------------------------------------------------------
+ * sigma[j] (the PSF's width in voxels along dims[j] of Data), the iteration count and the floor are state of
+ * the handle.  The resident emission buffer, its upload statistics and its occupancy map are re-derived on
+ * the device from the unmodified upload, the deconvolution in front of the other derived steps:
+ * unmodified upload -> deconvolution -> smoothing -> label gains -> resident buffer.  Every render, slice
+ * and histogram call reads an ordinary resident volume and is unchanged.
+ * Value.  Let B(x) be exactly vr_smooth_host(x, sigma): the weights of vr_smooth_weights_host
+ * (R = ceil(2 sigma)), the one-axis pass of the smoothing along dims[0], dims[1], dims[2] in that order,
+ * indices clamped at the border, an axis with sigma 0 or one voxel skipped.  With y the unmodified upload
+ * (after the widening of a typed upload), n = iterations and every operation rounded once to fp32:
+ *     d = (y < 0.f) ? 0.f : y                     (NaN and -0 pass through)
+ *     u_0 = d
+ *     for k = 0 .. n-1:   c = B(u_k)
+ *                         g = (c > floor) ? c : floor      (a NaN in c gives floor)
+ *                         r = d / g                        (one correctly rounded fp32 division)
+ *                         m = B(r)
+ *                         u_{k+1} = u_k * m
+ * and the resident voxel is u_n.  The correlation step m = B(r) uses the same clamped filter as the blur:
+ * with symmetric weights that is the adjoint of B away from the border and not at it (within R voxels of a
+ * face the clamped filter's transpose would weigh the edge voxels differently; an exact border adjoint is
+ * not provided).  Nothing is flushed or tested beyond what is written above; NaN, inf, +-0 and subnormals
+ * follow IEEE.  No bit depends on how the kernels tile their work, on which buffers the iteration rotates
+ * through, or on whether an elementwise step is fused into a filter pass.  When every axis with a sigma
+ * has one voxel B is the identity and the iteration is still evaluated as written.  Smoothing and label
+ * gains apply to u_n: the result equals vr_label_gain_host(vr_smooth_host(vr_deconvolve_host(y))).
+ * Off.  With iterations = 0, with every sigma zero or with sigma NULL no deconvolution is set (the getter
+ * then reports zeros), and every call does what it does without this feature.
+ * State left.  That of vr_sync_volumes of the host-deconvolved volume, bit for bit: the padded data with its
+ * apron (the edge replicate of the written interior), nonfinite and maxabs of the final values, a rebuilt
+ * occupancy map, a new upload version.  What is deconvolved is the buffer the handle's last
+ * vr_sync_volumes bound as emission; an absorption or reflection that aliases it follows; a separately
+ * uploaded volume, the gradient volumes of lookup mode and the LUT are not touched.
+ * When.  Eagerly inside vr_set_deconvolution, at the end of vr_sync_volumes (also per channel in
+ * vr_render_channels), inside vr_set_smoothing, vr_sync_labels and vr_set_label_gains (they derive again
+ * from the upload, the iterations included); nothing is written when nothing changed.  A rewrite waits for
+ * every launch that reads the buffer, so a *_device call in flight sees the volume it was launched on.  A
+ * failed pass leaves the unmodified upload behind, and a vr_set_deconvolution that failed so leaves no
+ * deconvolution set.
+ * Memory.  While a deconvolution is set the one unmodified copy, shared with the smoothing and the label
+ * gains, counts in the handle's required memory; during a derivation one scratch volume, and a second one
+ * when more than one axis is filtered, come from the buffer pool and go back afterwards (the estimate
+ * lives in the resident buffer or the first scratch volume, and the update may write the buffer it reads).
+ * When they do not fit: VR_ERR_VRAM, and the state stays as it was.  'mem_info' has a line for the
+ * deconvolution while one is set.
+ * Errors.  Checked before the handle (they need no device), each VR_ERR_ARGUMENT: a NaN, negative or
+ * infinite sigma; a sigma above VR_SMOOTH_MAX_SIGMA; iterations outside 0..VR_DECONV_MAX_ITERATIONS; a
+ * floor that is not finite and greater than 0 (also when the call clears).  VR_ERR_UNSUPPORTED, the message
+ * names the deconvolution: setting one on a multi-device group handle; vr_render_slab on a handle with one
+ * set (a slab's z border would be clamped where the whole volume has neighbouring planes). */
+#define VR_DECONV_MAX_ITERATIONS 64
+int vr_set_deconvolution(vr_context *h, const float sigma[3], int32_t iterations, float floor); /* NULL, zeros or 0 iterations clear */
+int vr_get_deconvolution(vr_context *h, float sigma[3], int32_t *iterations, float *floor);
+
+/* The value rule above on the CPU (needs no device), by vr_smooth_host's one-axis pass and the inline
+ * functions the kernels evaluate (csrc/vr_deconv.h): dst = u_n of src, both dense dims[0] x dims[1] x
+ * dims[2] column-major; dst may be src.  iterations = 0 or every sigma zero: a bit-exact copy.  The argument
+ * checks of vr_set_deconvolution; a NULL pointer is VR_ERR_ARGUMENT. */
+int vr_deconvolve_host(const float *src, const uint64_t dims[3], const float sigma[3], int32_t iterations, float floor,
+                       float *dst);
+
 /* --- slice views: axis-aligned, oblique and thick-slab sections of a resident volume (no reference
  * counterpart; MATLAB's sliceViewer / obliqueslice, a radiologist's MPR) ------------------------------
  * The sampler of every render evaluated on a plane instead of along camera rays: what the renderer shows

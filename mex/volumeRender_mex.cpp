@@ -560,5 +560,59 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     check(vr_set_smoothing(h, sigma));
     return;
   }
+  if (!strcmp(cmd, "set_deconvolution")) {
+    // volumeRender('set_deconvolution', h, sigma, iterations[, floor]) (vr_set_deconvolution): the Gaussian
+    // PSF's sigma in voxels, a single or double scalar (all three dimensions of Data) or 3-vector; iterations
+    // an integer-valued real scalar in 0..64; floor a single or double scalar (default 1e-6 single).  [] or
+    // false as sigma, or iterations = 0, clears.  The emission volume on the device follows at once; the
+    // setting stays with the handle.
+    if (nlhs > 0) mexErrMsgTxt("Too many output arguments.");
+    if (nrhs < 3) mexErrMsgTxt("insufficient parameter!");
+    if (nrhs > 5) mexErrMsgTxt("set_deconvolution: too many input arguments");
+    const mxArray *g = prhs[2];
+    const char *bad = "set_deconvolution: sigma must be a single or double scalar or 3-vector, [] or false";
+    const float default_floor = 1e-6f;
+    float flr = default_floor;
+    if (nrhs > 4) {
+      const mxArray *f = prhs[4];
+      const bool f32 = mxGetClassID(f) == mxSINGLE_CLASS;
+      if ((!f32 && mxGetClassID(f) != mxDOUBLE_CLASS) || mxIsComplex(f) || mxGetNumberOfElements(f) != 1)
+        mexErrMsgTxt("set_deconvolution: floor must be a real scalar greater than 0");
+      flr = f32 ? *static_cast<const float *>(mxGetData(f)) : (float)*static_cast<const double *>(mxGetData(f));
+    }
+    int32_t iterations = 0;
+    if (nrhs > 3) {
+      const mxArray *it = prhs[3];
+      const char *badn = "set_deconvolution: iterations must be an integer scalar in 0..64";
+      const mxClassID cls = mxGetClassID(it);  // any real numeric class
+      if (cls < mxDOUBLE_CLASS || cls > mxUINT64_CLASS || mxIsComplex(it) || mxGetNumberOfElements(it) != 1)
+        mexErrMsgTxt(badn);
+      const double v = mxGetScalar(it);
+      if (!(v >= 0.0 && v <= (double)VR_DECONV_MAX_ITERATIONS) || v != (double)(int32_t)v) mexErrMsgTxt(badn);
+      iterations = (int32_t)v;
+    }
+    if (mxIsClass(g, "logical")) {
+      if (mxGetNumberOfElements(g) != 1 || mxGetScalar(g) != 0.0) mexErrMsgTxt(bad);
+      check(vr_set_deconvolution(h, nullptr, 0, flr));
+      return;
+    }
+    const size_t n = mxGetNumberOfElements(g);
+    const bool f32 = mxGetClassID(g) == mxSINGLE_CLASS;
+    if ((!f32 && mxGetClassID(g) != mxDOUBLE_CLASS) || mxIsComplex(g) || mxGetNumberOfDimensions(g) != 2)
+      mexErrMsgTxt(bad);
+    if (n == 0) {
+      check(vr_set_deconvolution(h, nullptr, 0, flr));
+      return;
+    }
+    if ((mxGetM(g) != 1 && mxGetN(g) != 1) || (n != 1 && n != 3)) mexErrMsgTxt(bad);
+    if (nrhs < 4) mexErrMsgTxt("set_deconvolution: iterations is missing");
+    float sigma[3];
+    for (size_t j = 0; j < 3; ++j) {
+      const size_t k = n == 1 ? 0 : j;
+      sigma[j] = f32 ? static_cast<const float *>(mxGetData(g))[k] : (float)static_cast<const double *>(mxGetData(g))[k];
+    }
+    check(vr_set_deconvolution(h, sigma, iterations, flr));
+    return;
+  }
   mexErrMsgTxt(("Unknown command: " + std::string(cmd)).c_str());
 }

@@ -28,6 +28,9 @@ VR_CLIP_MAX = 6
 VR_LABEL_GAINS_MAX = 256
 VR_SMOOTH_MAX_SIGMA = 6.0
 VR_SMOOTH_MAX_TAPS = 25
+VR_DECONV_MAX_ITERATIONS = 64
+VR_EPI_FILTER, VR_EPI_RATIO, VR_EPI_UPDATE = 1, 2, 3  # csrc/vr_deconv.h
+VR_EPI_LOAD_DATA, VR_EPI_AUX_DATA = 1, 2
 # enum vr_slice_mode, enum vr_slice_source, VR_SLICE_MAX_SAMPLES
 VR_SLICE_MAX, VR_SLICE_MIN, VR_SLICE_SUM = 0, 1, 2
 VR_SLICE_EMISSION, VR_SLICE_ABSORPTION, VR_SLICE_REFLECTION = 0, 1, 2
@@ -114,6 +117,10 @@ _lib = None
 TOOL_SIGNATURES = [
     ("vr_smooth_axis_device", c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
     ("vr_smooth_fused_device", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("vr_deconv_axis_device", c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_float,
+                                      c_uint32, c_void_p, c_void_p]),
+    ("vr_debug_emission_version", c_int, [c_void_p, POINTER(c_uint64)]),
+    ("vr_deconv_pointwise_device", c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_float, c_uint32, c_void_p]),
     ("vr_debug_read_emission", c_int, [c_void_p, c_uint64, c_uint64, c_void_p]),
     ("vr_debug_derive_times", c_int, [c_void_p, c_void_p]),
 ]
@@ -160,6 +167,9 @@ SIGNATURES = [
     ("vr_get_smoothing", c_int, [c_void_p, c_void_p]),
     ("vr_smooth_weights_host", c_int, [c_float, POINTER(c_int32), c_void_p]),
     ("vr_smooth_host", c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("vr_set_deconvolution", c_int, [c_void_p, c_void_p, c_int32, c_float]),
+    ("vr_get_deconvolution", c_int, [c_void_p, c_void_p, POINTER(c_int32), POINTER(c_float)]),
+    ("vr_deconvolve_host", c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_float, c_void_p]),
     ("vr_render_slice", c_int, [c_void_p, POINTER(VrSlice), c_void_p, c_void_p, c_void_p]),
     ("vr_render_slice_device", c_int, [c_void_p, POINTER(VrSlice), c_void_p, c_void_p, c_void_p, c_void_p]),
     ("vr_slice_axis", c_int, [POINTER(c_uint64), c_int32, ctypes.c_double, c_uint64, POINTER(VrSlice)]),

@@ -181,6 +181,8 @@ int vr_delete(vr_context *h) {
     h->d_gains = nullptr;
     if (h->d_smooth_w) (void)hipFree(h->d_smooth_w);
     h->d_smooth_w = nullptr;
+    if (h->d_deconv_w) (void)hipFree(h->d_deconv_w);
+    h->d_deconv_w = nullptr;
   }
   g_contexts.erase(h);
   h->signature = 0;
@@ -224,6 +226,10 @@ int vr_mem_info(vr_context *h, char *buf, size_t buflen) {
   if (smoothing_set(h))  // (only while one is set: without, the report is what it was)
     os << "\t\tsmoothing sigma (voxels): " << h->smooth_sigma[0] << " " << h->smooth_sigma[1] << " "
        << h->smooth_sigma[2] << ", derived from the unmodified emission copy above\n";
+  if (deconvolution_set(h))
+    os << "\t\tdeconvolution sigma (voxels): " << h->deconv_sigma[0] << " " << h->deconv_sigma[1] << " "
+       << h->deconv_sigma[2] << ", iterations: " << h->deconv_iterations << ", floor: " << h->deconv_floor
+       << ", derived from the unmodified emission copy above\n";
   os << "\t\treusable buffers (MB): " << mb(vr_host::pool_bytes(h->device)) << "\n\n"
      << "\t\tSimilarity of Volumes\n\t\t---------------------\n"
      << "\t\t\tEm\tAb\tRe\n"
@@ -878,6 +884,119 @@ int vr_smooth_host(const float *src, const uint64_t dims[3], const float sigma[3
   return VR_OK;
 }
 
+int vr_set_deconvolution(vr_context *h, const float sigma[3], int32_t iterations, float flr) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (int rc = check_deconvolution(sigma, iterations, flr)) return rc;
+  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
+  // one form of "none": no sigma, no iterations, no floor
+  const bool any = sigma && iterations > 0 && (sigma[0] != 0.f || sigma[1] != 0.f || sigma[2] != 0.f);
+  const float sg[3] = {any ? sigma[0] + 0.f : 0.f, any ? sigma[1] + 0.f : 0.f, any ? sigma[2] + 0.f : 0.f};
+  const int32_t it = any ? iterations : 0;
+  const float fl = any ? flr : 0.f;
+  if (any && !h->children.empty()) return deconvolution_unsupported("vr_set_deconvolution");
+  if (sg[0] == h->deconv_sigma[0] && sg[1] == h->deconv_sigma[1] && sg[2] == h->deconv_sigma[2] &&
+      it == h->deconv_iterations && fl == h->deconv_floor)
+    return VR_OK;  // no change
+  VR_GUARD_BEGIN
+  DeviceGuard dg(h->device);
+  vr_host::prune_retired();
+  const float old[3] = {h->deconv_sigma[0], h->deconv_sigma[1], h->deconv_sigma[2]};
+  const int32_t old_it = h->deconv_iterations;
+  const float old_fl = h->deconv_floor;
+  const uint64_t old_version = h->deconv_version;
+  auto set = [h](const float *s3, int32_t n, float f, uint64_t version) {
+    for (int j = 0; j < 3; ++j) h->deconv_sigma[j] = s3[j];
+    h->deconv_iterations = n;
+    h->deconv_floor = f;
+    h->deconv_version = version;
+  };
+  set(sg, it, fl, next_version());
+  int rc = VR_OK;
+  try {
+    rc = apply_derived(h);
+  } catch (...) {  // a failed pass left the unmodified upload: the handle says so (no deconvolution), and the
+    const float zero[3] = {0.f, 0.f, 0.f};  // same setting given again is a change and derives again
+    set(zero, 0, 0.f, next_version());
+    throw;
+  }
+  if (rc == VR_ERR_VRAM) set(old, old_it, old_fl, old_version);  // nothing was written: the state stays as it was
+  return rc;
+  VR_GUARD_END
+}
+
+int vr_get_deconvolution(vr_context *h, float sigma[3], int32_t *iterations, float *flr) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!sigma || !iterations || !flr) return fail(VR_ERR_ARGUMENT, "deconvolution: sigma / iterations / floor is NULL");
+  if (!valid(h)) return fail(VR_ERR_HANDLE, "Handle not valid.");
+  for (int j = 0; j < 3; ++j) sigma[j] = h->deconv_sigma[j];
+  *iterations = h->deconv_iterations;
+  *flr = h->deconv_floor;
+  return VR_OK;
+}
+
+int vr_deconvolve_host(const float *src, const uint64_t dims[3], const float sigma[3], int32_t iterations, float flr,
+                       float *dst) {
+  if (int rc = check_deconvolution(sigma, iterations, flr)) return rc;
+  if (!dims || !sigma) return fail(VR_ERR_ARGUMENT, "deconvolution: dims / sigma is NULL");
+  if (dims[0] > 0x7FFFFFFF || dims[1] > 0x7FFFFFFF || dims[2] > 0x7FFFFFFF)
+    return fail(VR_ERR_UNSUPPORTED, "deconvolution: volume dimension too large");
+  const uint64_t count = dims[0] * dims[1] * dims[2];
+  if (!count) return VR_OK;
+  if (!src || !dst) return fail(VR_ERR_ARGUMENT, "deconvolution: src / dst is NULL");
+  if (iterations == 0 || (sigma[0] == 0.f && sigma[1] == 0.f && sigma[2] == 0.f)) {  // off: a copy
+    if (dst != src) std::memcpy(dst, src, count * sizeof(float));
+    return VR_OK;
+  }
+  try {
+    // y is read to the end (dst may be src); u the estimate, t the blurred estimate, then the ratio and
+    // the blurred ratio.  B is vr_smooth_host: vr_smooth_tap per active axis, which may work in place.
+    const std::vector<float> y(src, src + count);
+    std::vector<float> u(count), t(count);
+    for (uint64_t i = 0; i < count; ++i) u[i] = vr_deconv_data(y[i]);
+    for (int32_t k = 0; k < iterations; ++k) {
+      if (int rc = vr_smooth_host(u.data(), dims, sigma, t.data())) return rc;
+      for (uint64_t i = 0; i < count; ++i) t[i] = vr_deconv_ratio(y[i], t[i], flr);
+      if (int rc = vr_smooth_host(t.data(), dims, sigma, t.data())) return rc;
+      for (uint64_t i = 0; i < count; ++i) u[i] = vr_deconv_update(u[i], t[i]);
+    }
+    std::memcpy(dst, u.data(), count * sizeof(float));
+  } catch (const std::bad_alloc &) {
+    return fail(VR_ERR_DEVICE, "host out of memory");
+  }
+  return VR_OK;
+}
+
+// Measurement entries of tools/deconv_bench.py, not part of include/vrhip.h: one filter pass with an epilogue
+// of the deconvolution (epi, flags: csrc/vr_deconv.h VR_EPI_*; d_aux may be d_dst for the update), or one of
+// the two elementwise steps as a launch of its own, between caller-owned padded device buffers.
+extern "C" int vr_deconv_axis_device(const float *d_src, float *d_dst, const uint64_t dims[3], int32_t axis,
+                                     const float *d_weights, int32_t radius, int32_t epi, const float *d_aux, float flr,
+                                     uint32_t flags, void *d_stats, void *stream) {
+  if (!d_src || !d_dst || d_src == d_dst || !dims || !d_weights || axis < 0 || axis > 2 || radius < 1 ||
+      radius > VR_SMOOTH_MAX_RADIUS || !dims[0] || !dims[1] || !dims[2] || dims[0] > 0x7FFFFFFF ||
+      dims[1] > 0x7FFFFFFF || dims[2] > 0x7FFFFFFF || epi < VR_EPI_FILTER || epi > VR_EPI_UPDATE ||
+      (epi != VR_EPI_FILTER && !d_aux) || (epi != VR_EPI_UPDATE && (d_stats || d_aux == d_dst)))
+    return fail(VR_ERR_ARGUMENT, "deconvolution: invalid pass arguments");
+  VR_GUARD_BEGIN
+  VR_HIP(vr::launch_deconv_axis(d_src, d_dst, (int32_t)dims[0], (int32_t)dims[1], (int32_t)dims[2], axis, d_weights,
+                                radius, epi, d_aux, flr, flags, static_cast<vr::BufStats *>(d_stats),
+                                (hipStream_t)stream));
+  return VR_OK;
+  VR_GUARD_END
+}
+
+extern "C" int vr_deconv_pointwise_device(const float *d_src, float *d_dst, const uint64_t dims[3], int32_t epi,
+                                          const float *d_aux, float flr, uint32_t flags, void *stream) {
+  if (!d_src || !d_dst || !d_aux || !dims || !dims[0] || !dims[1] || !dims[2] || dims[0] > 0x7FFFFFFF ||
+      dims[1] > 0x7FFFFFFF || dims[2] > 0x7FFFFFFF || (epi != VR_EPI_RATIO && epi != VR_EPI_UPDATE))
+    return fail(VR_ERR_ARGUMENT, "deconvolution: invalid pass arguments");
+  VR_GUARD_BEGIN
+  VR_HIP(vr::launch_deconv_pointwise(d_src, d_dst, (int32_t)dims[0], (int32_t)dims[1], (int32_t)dims[2], epi, d_aux,
+                                     flr, flags, (hipStream_t)stream));
+  return VR_OK;
+  VR_GUARD_END
+}
+
 // Measurement entries of tools/smooth_bench.py, not part of include/vrhip.h: one axis pass, or the fused
 // launch, between two padded device buffers (d_weights: 3 x 25 floats for the fused form, 2 radius + 1 for
 // a pass), and a read-back of `count` floats at element `offset` of the handle's resident emission buffer.
@@ -912,6 +1031,16 @@ extern "C" int vr_debug_derive_times(vr_context *h, double out[2]) {
   if (!valid(h) || !out) return fail(VR_ERR_HANDLE, "Handle not valid.");
   out[0] = h->derive_ms[0];
   out[1] = h->derive_ms[1];
+  return VR_OK;
+}
+
+// The upload version of the handle's resident emission buffer (0: none): every upload and every derivation
+// takes a new one, so an unchanged version says that nothing was written.
+extern "C" int vr_debug_emission_version(vr_context *h, uint64_t *version) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!valid(h) || !version) return fail(VR_ERR_HANDLE, "Handle not valid.");
+  const BufPtr b = label_target(h);
+  *version = b ? b->version : 0;
   return VR_OK;
 }
 
@@ -969,6 +1098,7 @@ int vr_render_slab(vr_context *h, const vr_render_args *a, const vr_slab *slab, 
   if (!a) return fail(VR_ERR_ARGUMENT, "insufficient parameter!");
   if (h->nclip) return clip_unsupported("vr_render_slab");
   if (smoothing_set(h)) return smoothing_unsupported("vr_render_slab");
+  if (deconvolution_set(h)) return deconvolution_unsupported("vr_render_slab");
   VR_GUARD_BEGIN
   DeviceGuard dg(h->device);
   vr_host::prune_retired();  // buffers whose last launch has completed

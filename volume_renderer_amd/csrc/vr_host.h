@@ -2,7 +2,7 @@
 // handle and the module state's types, the checked-call and entry-guard macros, the tuning constants,
 // the shared state (vr_state.hip) and the functions that cross files, all in namespace vr_host.
 //   vr_state.hip     the shared state, the switches, the stream pool, the kernel files' callbacks
-//   vr_sync.hip      upload and slot state machine, memory checks, smoothing and label gains, do_sync_volumes
+//   vr_sync.hip      upload and slot state machine, memory checks, deconvolution, smoothing and label gains, do_sync_volumes
 //   vr_frame.hip     clip conversion, build_frame, lights, partition, depth lanes, the march entry table, schedules
 //   vr_render.hip    do_render, do_render_slab, the multi-device group, view sets / channels
 //   vr_features.hip  projection, slice, isosurface and transfer renders, the volume histogram
@@ -24,6 +24,7 @@
 #include "vr_launch.h"
 #include "vr_resources.h"
 #include "vr_slice.h"
+#include "vr_deconv.h"
 #include "vr_smooth.h"
 
 #ifndef VR_DEPTH_ROUNDS_K1
@@ -138,11 +139,13 @@ struct DevBuf {
   // are those of the modulated values; mod_labels / mod_gains name the label upload and the gain
   // table that ptr was derived from.  Only the label pass reads orig, and the host waits for it.
   // Smoothing (vr_set_smoothing) shares the copy: ptr is orig smoothed, then modulated;
-  // mod_smooth names the sigma it was smoothed with (0: not smoothed).
+  // mod_smooth names the sigma it was smoothed with (0: not smoothed).  The deconvolution
+  // (vr_set_deconvolution) runs in front of both from the same copy; mod_deconv names its
+  // setting (0: none).
   float *orig = nullptr;
   bool orig_nonfinite = false;
   float orig_maxabs = 0.f;
-  uint64_t mod_labels = 0, mod_gains = 0, mod_smooth = 0;
+  uint64_t mod_labels = 0, mod_gains = 0, mod_smooth = 0, mod_deconv = 0;
   ~DevBuf() {
     if (orig) vr_host::pooled_free(orig, bytes, device, vr_host::Readers());
     if (zpair) vr_host::pooled_free(zpair, zpair_bytes, device, vr_host::Readers(readers));
@@ -244,6 +247,14 @@ struct vr_context {
   float smooth_sigma[3] = {0.f, 0.f, 0.f};
   uint64_t smooth_version = 0;
   float *d_smooth_w = nullptr;
+  // Richardson-Lucy deconvolution (vr_set_deconvolution): the PSF's sigma per axis of Data,
+  // the iteration count (0: none) and the floor as the caller gave them, the version that keys
+  // DevBuf::mod_deconv, and the device copy of the three axes' weights
+  float deconv_sigma[3] = {0.f, 0.f, 0.f};
+  int32_t deconv_iterations = 0;
+  float deconv_floor = 0.f;
+  uint64_t deconv_version = 0;
+  float *d_deconv_w = nullptr;
   // the last derivation's host-clock times (ms), each ending in a stream synchronise: the passes with the
   // statistics read-back, the occupancy rebuild (tools/smooth_bench.py reads them)
   double derive_ms[2] = {0.0, 0.0};
@@ -369,6 +380,9 @@ int apply_derived(vr_context *h);
 bool smoothing_set(const vr_context *h);
 int check_smoothing(const float sigma[3]);
 int smoothing_unsupported(const char *what);
+bool deconvolution_set(const vr_context *h);
+int check_deconvolution(const float sigma[3], int32_t iterations, float flr);
+int deconvolution_unsupported(const char *what);
 void free_labels(vr_context *h);
 int labels_unsupported(const char *what);
 int check_label_gains(const float *gains, int32_t n);

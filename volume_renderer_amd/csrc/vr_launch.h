@@ -79,6 +79,14 @@ hipError_t launch_label_gain(const float *src, const uint8_t *labels, const floa
 // padded; wts: the 2R+1 weights in device memory; st null, or *st += the statistics of dst
 hipError_t launch_smooth_axis(const float *src, float *dst, int32_t nx, int32_t ny, int32_t nz, int axis,
                               const float *wts, int32_t R, BufStats *st, hipStream_t s);
+// vr_smooth.hip: the same pass with an epilogue of the deconvolution (vr_deconv.h VR_EPI_*): aux the
+// auxiliary padded buffer (for VR_EPI_UPDATE it may be dst), flr the floor; st only with VR_EPI_UPDATE
+hipError_t launch_deconv_axis(const float *src, float *dst, int32_t nx, int32_t ny, int32_t nz, int axis,
+                              const float *wts, int32_t R, int epi, const float *aux, float flr, uint32_t flags,
+                              BufStats *st, hipStream_t s);
+// vr_deconv.hip: the ratio or the update as an elementwise launch over the padded volume (dst may be src or aux)
+hipError_t launch_deconv_pointwise(const float *src, float *dst, int32_t nx, int32_t ny, int32_t nz, int epi,
+                                   const float *aux, float flr, uint32_t flags, hipStream_t s);
 // vr_smooth.hip: the three axes in one launch (every dim >= 2, every radius >= 1); wts: 3 x 25 weights
 hipError_t launch_smooth_fused(const float *src, float *dst, int32_t nx, int32_t ny, int32_t nz, const float *wts,
                                int32_t Rx, int32_t Ry, int32_t Rz, BufStats *st, hipStream_t s);

@@ -5,8 +5,13 @@
 // outputs are computed at clamped coordinates, and the two apron cells of the filtered axis are stored
 // with the edge outputs; along the other two axes the apron lines are filtered like any line (they
 // replicate an interior line, so their outputs replicate that line's outputs bit for bit).
+// The Richardson-Lucy deconvolution (vr_set_deconvolution) runs the same passes with an
+// epilogue on the last axis of each blur (template parameter EPI): the output voxel's ratio or update
+// (vr_deconv.h) is formed from the filter's value and the voxel of an auxiliary padded buffer at the same
+// position, and stored in its place -- the apron cells as above, so no pad pass follows.
 #include <hip/hip_runtime.h>
 
+#include "vr_deconv.h"
 #include "vr_device.h"
 #include "vr_smooth.h"
 
@@ -15,6 +20,33 @@ namespace vr {
 #define VR_SMOOTH_SEG 256   // x pass: outputs per staged row segment, one per lane
 #define VR_SMOOTH_TX 64     // y / z pass: the tile's lanes along x, one wave wide
 #define VR_SMOOTH_TA 32     // y / z pass: the tile's outputs along the filtered axis (8 per wave of the 4)
+
+// EPI of a pass: 0 the smoothing's own (no epilogue, flags ignored); the others serve the deconvolution and
+// take `flags`: VR_EPI_LOAD_DATA: the loads of src go through vr_deconv_data (src is the unmodified upload,
+// iteration 0), VR_EPI_AUX_DATA: so does the update's auxiliary voxel.
+//   VR_EPI_FILTER  the filter's value (a pass that only needs the load flag)
+//   VR_EPI_RATIO   vr_deconv_ratio(aux, value, flr), aux the unmodified upload
+//   VR_EPI_UPDATE  vr_deconv_update(aux, value), aux the estimate u; aux may be dst (each voxel is read
+//                  by the thread that then writes it, and the filtered axis' apron cells are not read)
+// With an epilogue neither dst nor aux is __restrict__.
+template <int EPI>
+struct smooth_dst {
+  typedef float *type;
+};
+template <>
+struct smooth_dst<0> {
+  typedef float *__restrict__ type;
+};
+
+template <int EPI>
+__device__ __forceinline__ float smooth_epilogue(float v, const float *aux, uint64_t at, float flr, uint32_t flags) {
+  if (EPI == VR_EPI_RATIO) return vr_deconv_ratio(aux[at], v, flr);
+  if (EPI == VR_EPI_UPDATE) {
+    const float a = aux[at];
+    return vr_deconv_update((flags & VR_EPI_AUX_DATA) ? vr_deconv_data(a) : a, v);
+  }
+  return v;
+}
 
 // nonfinite / max |x| of the written values, as in the upload and the label pass: one wave reduction
 // and one atomic pair per workgroup (256 threads).
@@ -41,10 +73,11 @@ __device__ __forceinline__ void smooth_fold_stats(uint32_t bad, float mx, BufSta
 // Along x: one padded row per workgroup iteration (as label_gain_kernel), in segments of VR_SMOOTH_SEG
 // interior voxels staged in LDS with their halo of R on either side at clamped coordinates; lane t
 // computes output t of the segment from consecutive LDS words (no bank conflict).
-template <bool STATS>
-__global__ __launch_bounds__(256) void smooth_x_kernel(const float *__restrict__ src, float *__restrict__ dst,
+template <bool STATS, int EPI>
+__global__ __launch_bounds__(256) void smooth_x_kernel(const float *__restrict__ src, typename smooth_dst<EPI>::type dst,
                                                        int32_t nx, uint64_t rows, const float *__restrict__ wts,
-                                                       int32_t R, BufStats *st) {
+                                                       int32_t R, BufStats *st, const float *aux, float flr,
+                                                       uint32_t flags) {
   __shared__ float w[VR_SMOOTH_MAX_TAPS];
   __shared__ float line[VR_SMOOTH_SEG + 2 * VR_SMOOTH_MAX_RADIUS];
   if ((int32_t)threadIdx.x <= 2 * R) w[threadIdx.x] = wts[threadIdx.x];
@@ -60,13 +93,14 @@ __global__ __launch_bounds__(256) void smooth_x_kernel(const float *__restrict__
       for (int32_t t = (int32_t)threadIdx.x; t < cnt + 2 * R; t += 256) {
         int32_t c = a0 - R + t;
         c = c < 0 ? 0 : (c > nx - 1 ? nx - 1 : c);
-        line[t] = s[c];
+        line[t] = (EPI && (flags & VR_EPI_LOAD_DATA)) ? vr_deconv_data(s[c]) : s[c];
       }
       __syncthreads();
       for (int32_t u = (int32_t)threadIdx.x; u < cnt; u += 256) {
         const float *x = line + u;
-        const float v = vr_smooth_tap(w, R, [x](int32_t k) { return x[k]; });
         const int32_t c = a0 + u;
+        const float v = smooth_epilogue<EPI>(vr_smooth_tap(w, R, [x](int32_t k) { return x[k]; }), aux,
+                                             row * px + 1 + (uint64_t)c, flr, flags);
         d[c] = v;
         if (c == 0) d[-1] = v;
         if (c == nx - 1) d[nx] = v;
@@ -88,11 +122,12 @@ __global__ __launch_bounds__(256) void smooth_x_kernel(const float *__restrict__
 // turn; wave v then computes the tile's outputs v, v + 4, ... from LDS column `lane`.
 //   n: interior length of the filtered axis, astride its element stride, ostride the third axis',
 //   no the third axis' padded length, px the padded row length.
-template <bool STATS>
-__global__ __launch_bounds__(256) void smooth_s_kernel(const float *__restrict__ src, float *__restrict__ dst,
+template <bool STATS, int EPI>
+__global__ __launch_bounds__(256) void smooth_s_kernel(const float *__restrict__ src, typename smooth_dst<EPI>::type dst,
                                                        uint32_t px, int32_t n, uint64_t astride, uint32_t no,
                                                        uint64_t ostride, uint64_t tiles,
-                                                       const float *__restrict__ wts, int32_t R, BufStats *st) {
+                                                       const float *__restrict__ wts, int32_t R, BufStats *st,
+                                                       const float *aux, float flr, uint32_t flags) {
   __shared__ float w[VR_SMOOTH_MAX_TAPS];
   __shared__ float tile[VR_SMOOTH_TA + 2 * VR_SMOOTH_MAX_RADIUS][VR_SMOOTH_TX];
   if ((int32_t)threadIdx.x <= 2 * R) w[threadIdx.x] = wts[threadIdx.x];
@@ -114,14 +149,16 @@ __global__ __launch_bounds__(256) void smooth_s_kernel(const float *__restrict__
     for (int32_t l = (int32_t)wave; l < cnt + 2 * R; l += 4) {
       int32_t c = a0 - R + l;
       c = c < 0 ? 0 : (c > n - 1 ? n - 1 : c);
-      tile[l][lane] = in ? src[base + (uint64_t)(c + 1) * astride] : 0.f;
+      const float xv = in ? src[base + (uint64_t)(c + 1) * astride] : 0.f;
+      tile[l][lane] = (EPI && (flags & VR_EPI_LOAD_DATA)) ? vr_deconv_data(xv) : xv;
     }
     __syncthreads();
     if (in) {
       for (int32_t u = (int32_t)wave; u < cnt; u += 4) {
         const float *x = &tile[u][lane];
-        const float v = vr_smooth_tap(w, R, [x](int32_t k) { return x[k * VR_SMOOTH_TX]; });
         const int32_t c = a0 + u;
+        const float v = smooth_epilogue<EPI>(vr_smooth_tap(w, R, [x](int32_t k) { return x[k * VR_SMOOTH_TX]; }), aux,
+                                             base + (uint64_t)(c + 1) * astride, flr, flags);
         dst[base + (uint64_t)(c + 1) * astride] = v;
         if (c == 0) dst[base] = v;
         if (c == n - 1) dst[base + (uint64_t)(n + 1) * astride] = v;
@@ -139,17 +176,16 @@ __global__ __launch_bounds__(256) void smooth_s_kernel(const float *__restrict__
 // One axis pass, src -> dst (both padded (nx+2)(ny+2)(nz+2) floats, src with its apron in place, not
 // aliasing): axis 0 / 1 / 2 along dims[0] / [1] / [2]; wts the 2R+1 weights in device memory, R in
 // 1..VR_SMOOTH_MAX_RADIUS; st (may be null): *st += the statistics of dst.
-hipError_t launch_smooth_axis(const float *src, float *dst, int32_t nx, int32_t ny, int32_t nz, int axis,
-                              const float *wts, int32_t R, BufStats *st, hipStream_t s) {
-  if (nx <= 0 || ny <= 0 || nz <= 0 || axis < 0 || axis > 2 || R < 1 || R > VR_SMOOTH_MAX_RADIUS || !src || !dst ||
-      src == dst || !wts)
-    return hipErrorInvalidValue;
+template <bool STATS, int EPI>
+static hipError_t launch_axis(const float *src, float *dst, int32_t nx, int32_t ny, int32_t nz, int axis,
+                              const float *wts, int32_t R, BufStats *st, const float *aux, float flr, uint32_t flags,
+                              hipStream_t s) {
   const uint64_t px = (uint64_t)nx + 2, py = (uint64_t)ny + 2, pz = (uint64_t)nz + 2;
   if (axis == 0) {
     const uint64_t rows = py * pz;
     const unsigned blocks = (unsigned)(rows < 4096 ? rows : 4096);
-    if (st) hipLaunchKernelGGL(smooth_x_kernel<true>, dim3(blocks), dim3(256), 0, s, src, dst, nx, rows, wts, R, st);
-    else hipLaunchKernelGGL(smooth_x_kernel<false>, dim3(blocks), dim3(256), 0, s, src, dst, nx, rows, wts, R, st);
+    hipLaunchKernelGGL((smooth_x_kernel<STATS, EPI>), dim3(blocks), dim3(256), 0, s, src, dst, nx, rows, wts, R, st, aux,
+                       flr, flags);
     return hipGetLastError();
   }
   const int32_t n = axis == 1 ? ny : nz;
@@ -157,13 +193,43 @@ hipError_t launch_smooth_axis(const float *src, float *dst, int32_t nx, int32_t 
   const uint64_t no = axis == 1 ? pz : py;
   const uint64_t tiles = ((px + VR_SMOOTH_TX - 1) / VR_SMOOTH_TX) * (((uint64_t)n + VR_SMOOTH_TA - 1) / VR_SMOOTH_TA) * no;
   const unsigned blocks = (unsigned)(tiles < (1u << 16) ? tiles : (1u << 16));
-  if (st)
-    hipLaunchKernelGGL(smooth_s_kernel<true>, dim3(blocks), dim3(256), 0, s, src, dst, (uint32_t)px, n, astride,
-                       (uint32_t)no, ostride, tiles, wts, R, st);
-  else
-    hipLaunchKernelGGL(smooth_s_kernel<false>, dim3(blocks), dim3(256), 0, s, src, dst, (uint32_t)px, n, astride,
-                       (uint32_t)no, ostride, tiles, wts, R, st);
+  hipLaunchKernelGGL((smooth_s_kernel<STATS, EPI>), dim3(blocks), dim3(256), 0, s, src, dst, (uint32_t)px, n, astride,
+                     (uint32_t)no, ostride, tiles, wts, R, st, aux, flr, flags);
   return hipGetLastError();
+}
+
+static bool axis_args_ok(const float *src, const float *dst, int32_t nx, int32_t ny, int32_t nz, int axis,
+                         const float *wts, int32_t R) {
+  return nx > 0 && ny > 0 && nz > 0 && axis >= 0 && axis <= 2 && R >= 1 && R <= VR_SMOOTH_MAX_RADIUS && src && dst &&
+         src != dst && wts;
+}
+
+hipError_t launch_smooth_axis(const float *src, float *dst, int32_t nx, int32_t ny, int32_t nz, int axis,
+                              const float *wts, int32_t R, BufStats *st, hipStream_t s) {
+  if (!axis_args_ok(src, dst, nx, ny, nz, axis, wts, R)) return hipErrorInvalidValue;
+  return st ? launch_axis<true, 0>(src, dst, nx, ny, nz, axis, wts, R, st, nullptr, 0.f, 0u, s)
+            : launch_axis<false, 0>(src, dst, nx, ny, nz, axis, wts, R, st, nullptr, 0.f, 0u, s);
+}
+
+// The same pass with an epilogue of the deconvolution (epi = VR_EPI_FILTER / RATIO / UPDATE and flags as
+// above): aux the auxiliary padded buffer (RATIO, UPDATE; for UPDATE it may be dst), flr the rule's floor.
+// Statistics are formed only by the update, whose output can be the final buffer.
+hipError_t launch_deconv_axis(const float *src, float *dst, int32_t nx, int32_t ny, int32_t nz, int axis,
+                              const float *wts, int32_t R, int epi, const float *aux, float flr, uint32_t flags,
+                              BufStats *st, hipStream_t s) {
+  if (!axis_args_ok(src, dst, nx, ny, nz, axis, wts, R) || (epi != VR_EPI_FILTER && !aux) ||
+      (epi != VR_EPI_UPDATE && (st || aux == dst)))
+    return hipErrorInvalidValue;
+  switch (epi) {
+    case VR_EPI_FILTER:
+      return launch_axis<false, VR_EPI_FILTER>(src, dst, nx, ny, nz, axis, wts, R, st, aux, flr, flags, s);
+    case VR_EPI_RATIO:
+      return launch_axis<false, VR_EPI_RATIO>(src, dst, nx, ny, nz, axis, wts, R, st, aux, flr, flags, s);
+    case VR_EPI_UPDATE:
+      return st ? launch_axis<true, VR_EPI_UPDATE>(src, dst, nx, ny, nz, axis, wts, R, st, aux, flr, flags, s)
+                : launch_axis<false, VR_EPI_UPDATE>(src, dst, nx, ny, nz, axis, wts, R, st, aux, flr, flags, s);
+  }
+  return hipErrorInvalidValue;
 }
 
 // ---- the fused form: all three axes in one launch, each voxel read about once ---------------------------

@@ -5,7 +5,8 @@
 //     re-expressed as host state: "textures" are bindings of device buffers (fp32 volumes resident in HBM,
 //     read by the software sampler of vr_kernels.hip), the slot indices d_idx* stay module-global exactly
 //     as in the reference
-//   - Gaussian smoothing and label gains, one derivation from the unmodified upload
+//   - deconvolution, Gaussian smoothing and label gains, one derivation from the unmodified upload
+//     
 #include "vr_host.h"
 
 namespace vr_host {
@@ -108,7 +109,7 @@ static void build_occupancy(DevBuf *b, hipStream_t s) {
 static void drop_unmodified_copy(DevBuf *b) {
   if (b->orig) vr_host::pooled_free(b->orig, b->bytes, b->device, vr_host::Readers());
   b->orig = nullptr;
-  b->mod_labels = b->mod_gains = b->mod_smooth = 0;
+  b->mod_labels = b->mod_gains = b->mod_smooth = b->mod_deconv = 0;
 }
 
 static void sync_volume(vr_context *h, int tex, int slot) {
@@ -192,8 +193,8 @@ uint64_t required_memory(const vr_context *h) {
   r += h->vol[T_DX].memory_size + h->vol[T_DY].memory_size + h->vol[T_DZ].memory_size;
   // label gains: the label bytes, and the unmodified copy of the emission volume while gains are set
   r += h->labels_bytes;
-  // (one copy, shared with the smoothing while a sigma is set)
-  if ((h->d_labels && h->ngains > 0) || smoothing_set(h)) r += em.memory_size;
+  // (one copy, shared with the smoothing and the deconvolution while either is set)
+  if ((h->d_labels && h->ngains > 0) || smoothing_set(h) || deconvolution_set(h)) r += em.memory_size;
   return r;
 }
 
@@ -276,7 +277,7 @@ static void restore_unmodified(DevBuf *b) {
   b->orig = nullptr;
   b->nonfinite = b->orig_nonfinite;
   b->maxabs = b->orig_maxabs;
-  b->mod_labels = b->mod_gains = b->mod_smooth = 0;
+  b->mod_labels = b->mod_gains = b->mod_smooth = b->mod_deconv = 0;
   b->version = next_version();
   build_occupancy(b, label_uploader(b->device).pad_stream);
 }
@@ -321,16 +322,93 @@ static bool smooth_fused(int32_t Rx, int32_t Ry, int32_t Rz) {
   return std::max(Rx, std::max(Ry, Rz)) <= VR_SMOOTH_FUSED_MAX_R;
 }
 
-// Bring the handle's emission buffer up to date with its smoothing, labels and gains, one derivation
-// from the unmodified upload: orig -> smoothing (one pass per axis with sigma > 0 and more than one
+// ---- Richardson-Lucy deconvolution (include/vrhip.h vr_set_deconvolution) --------------
+bool deconvolution_set(const vr_context *h) {
+  return h->deconv_iterations > 0 &&
+         (h->deconv_sigma[0] != 0.f || h->deconv_sigma[1] != 0.f || h->deconv_sigma[2] != 0.f);
+}
+
+int check_deconvolution(const float sigma[3], int32_t iterations, float flr) {
+  if (sigma)
+    for (int j = 0; j < 3; ++j) {
+      if (!(sigma[j] >= 0.f) || !std::isfinite(sigma[j]))
+        return fail(VR_ERR_ARGUMENT, "deconvolution: every sigma must be finite and not negative");
+      if (sigma[j] > VR_SMOOTH_MAX_SIGMA)
+        return fail(VR_ERR_ARGUMENT, "deconvolution: sigma must be at most 6 voxels");
+    }
+  if (iterations < 0 || iterations > VR_DECONV_MAX_ITERATIONS)
+    return fail(VR_ERR_ARGUMENT, "deconvolution: iterations must be in 0..64");
+  if (!(flr > 0.f) || !std::isfinite(flr))
+    return fail(VR_ERR_ARGUMENT, "deconvolution: floor must be finite and greater than 0");
+  return VR_OK;
+}
+
+int deconvolution_unsupported(const char *what) {
+  return fail(VR_ERR_UNSUPPORTED, std::string(what) + ": the deconvolution (vr_set_deconvolution) is not supported " +
+                                      (std::strcmp(what, "vr_render_slab") ? "on a multi-device group handle"
+                                                                           : "by a slab render: a slab's z border "
+                                                                             "would be clamped"));
+}
+
+// The iterations of the value rule on the device: y the unmodified upload, the estimate u_k in `u` (u_0 is
+// never stored: iteration 0 reads y through vr_deconv_data), t1 and t2 two further volumes, all padded
+// and distinct; axis[0..na-1] the active axes in ascending order with their radii R and the weights of
+// axis j at wts + j * VR_SMOOTH_MAX_TAPS.  One iteration is 2 na launches: the passes of B(u), whose last
+// stores the ratio into t1, and the passes of B(r), whose last stores the update into u -- reading u at
+// the voxel it writes when k > 0.  t2 is needed only with more than one active axis.  With no active axis
+// B is the identity and the two steps are elementwise launches.  st (may be null): the statistics of u_n.
+static void run_deconvolution(const float *y, float *u, float *t1, float *t2, int32_t nx, int32_t ny, int32_t nz,
+                              const int *axis, const int32_t *R, int na, const float *wts, int32_t iterations, float flr,
+                              vr::BufStats *st, hipStream_t s) {
+  for (int32_t k = 0; k < iterations; ++k) {
+    const bool first = k == 0, last = k == iterations - 1;
+    const float *cur = first ? y : u;
+    if (!na) {
+      VR_HIP(vr::launch_deconv_pointwise(cur, t1, nx, ny, nz, VR_EPI_RATIO, y, flr, first ? VR_EPI_LOAD_DATA : 0u, s));
+      VR_HIP(vr::launch_deconv_pointwise(t1, u, nx, ny, nz, VR_EPI_UPDATE, cur, flr, first ? VR_EPI_AUX_DATA : 0u, s));
+      if (last && st) VR_HIP(vr::launch_stats(u, ((uint64_t)nx + 2) * ((uint64_t)ny + 2) * ((uint64_t)nz + 2), st, s));
+      continue;
+    }
+    const float *src = cur;
+    for (int i = 0; i < na; ++i) {  // B(u); the last pass stores the ratio in t1
+      float *dst = (na - 1 - i) % 2 ? t2 : t1;
+      const float *w = wts + axis[i] * VR_SMOOTH_MAX_TAPS;
+      const uint32_t flags = first && i == 0 ? VR_EPI_LOAD_DATA : 0u;
+      if (i == na - 1)
+        VR_HIP(vr::launch_deconv_axis(src, dst, nx, ny, nz, axis[i], w, R[i], VR_EPI_RATIO, y, flr, flags, nullptr, s));
+      else if (flags)
+        VR_HIP(vr::launch_deconv_axis(src, dst, nx, ny, nz, axis[i], w, R[i], VR_EPI_FILTER, nullptr, flr, flags, nullptr, s));
+      else
+        VR_HIP(vr::launch_smooth_axis(src, dst, nx, ny, nz, axis[i], w, R[i], nullptr, s));
+      src = dst;
+    }
+    for (int i = 0; i < na; ++i) {  // B(r); the last pass stores the update in u
+      const float *w = wts + axis[i] * VR_SMOOTH_MAX_TAPS;
+      if (i == na - 1) {
+        VR_HIP(vr::launch_deconv_axis(src, u, nx, ny, nz, axis[i], w, R[i], VR_EPI_UPDATE, cur, flr,
+                                      first ? VR_EPI_AUX_DATA : 0u, last ? st : nullptr, s));
+      } else {
+        float *dst = src == t1 ? t2 : t1;
+        VR_HIP(vr::launch_smooth_axis(src, dst, nx, ny, nz, axis[i], w, R[i], nullptr, s));
+        src = dst;
+      }
+    }
+  }
+}
+
+// Bring the handle's emission buffer up to date with its deconvolution, smoothing, labels and gains, one
+// derivation from the unmodified upload: orig -> deconvolution (the iterations above over the axes with a
+// PSF sigma > 0 and more than one voxel) -> smoothing (one pass per axis with sigma > 0 and more than one
 // voxel, dims[0] first) -> label gains (when emission, labels and n > 0 are all present) -> ptr;
 // unmodified when no pass is left; nothing is written when nothing changed.
 // The first derivation of an upload takes a second buffer and swaps: the upload becomes the unmodified
 // copy, the last pass writes the new ptr (no copy of the volume).  Passes in between alternate between
-// ptr and one scratch volume from the pool, which goes back afterwards.  The statistics fold into the
+// ptr and one scratch volume from the pool, which goes back afterwards.  The deconvolution keeps its
+// estimate in whichever of the two lets the passes after it end in ptr, and rotates through the other
+// and, with more than one active axis, a second scratch volume.  The statistics fold into the
 // last pass.  The state left is that of an upload of the host-rewritten volume: data and apron,
 // statistics, occupancy map, a new version.  VR_ERR_VRAM (nothing changed) when the copy and the
-// scratch volume do not fit.
+// scratch volumes do not fit.
 int apply_derived(vr_context *h) {
   BufPtr b = label_target(h);
   if (!b || !b->ptr) return VR_OK;
@@ -353,15 +431,29 @@ int apply_derived(vr_context *h) {
     np = 1;
   }
   if (gain) pass[np++] = Pass{3, 0};
-  if (!np) {
+  // the deconvolution in front of them: its active axes (none: B is the identity, the rule still iterates)
+  const bool deconv = deconvolution_set(h);
+  int daxis[3], nda = 0;
+  int32_t dR[3];
+  float dwts[3 * VR_SMOOTH_MAX_TAPS] = {};
+  if (deconv)
+    for (int j = 0; j < 3; ++j)
+      if (h->deconv_sigma[j] > 0.f && b->dims[j] > 1) {
+        daxis[nda] = j;
+        dR[nda++] = vr_smooth_weights(h->deconv_sigma[j], dwts + j * VR_SMOOTH_MAX_TAPS);
+      }
+  if (!np && !deconv) {
     restore_unmodified(b.get());
     return bad;
   }
   const uint64_t kl = gain ? h->labels_version : 0, kg = gain ? h->gains_version : 0,
-                 ks = smooth ? h->smooth_version : 0;
-  if (b->orig && b->mod_labels == kl && b->mod_gains == kg && b->mod_smooth == ks) return bad;
-  if (smooth) {  // (the gain pass alone was checked by its caller, as before)
-    const uint64_t need = (b->orig ? 0 : b->bytes) + (np > 1 ? b->bytes : 0);
+                 ks = smooth ? h->smooth_version : 0, kd = deconv ? h->deconv_version : 0;
+  if (b->orig && b->mod_labels == kl && b->mod_gains == kg && b->mod_smooth == ks && b->mod_deconv == kd) return bad;
+  // scratch volumes: the passes alternate between ptr and one; the deconvolution's rotation takes that one
+  // and, with more than one active axis, a second
+  const int nscratch = deconv ? (nda > 1 ? 2 : 1) : (np > 1 ? 1 : 0);
+  if (smooth || deconv) {  // (the gain pass alone was checked by its caller, as before)
+    const uint64_t need = (b->orig ? 0 : b->bytes) + (uint64_t)nscratch * b->bytes;
     if (int rc = check_free_device_memory(need)) return rc;
   }
   vr_host::Uploader &U = label_uploader(b->device);
@@ -369,6 +461,8 @@ int apply_derived(vr_context *h) {
     VR_HIP(vr_host::device_alloc(reinterpret_cast<void **>(&h->d_gains), sizeof(h->gains)));
   if (smooth && !h->d_smooth_w)
     VR_HIP(vr_host::device_alloc(reinterpret_cast<void **>(&h->d_smooth_w), sizeof(wts)));
+  if (deconv && !h->d_deconv_w)
+    VR_HIP(vr_host::device_alloc(reinterpret_cast<void **>(&h->d_deconv_w), sizeof(dwts)));
   b->readers.wait();  // "neither rewritten nor freed before all of them": renders in flight keep their volume
   if (!b->orig) {
     float *fresh = nullptr;
@@ -378,16 +472,24 @@ int apply_derived(vr_context *h) {
     b->orig_nonfinite = b->nonfinite;
     b->orig_maxabs = b->maxabs;
   }
-  b->mod_labels = b->mod_gains = b->mod_smooth = 0;  // (until the passes below have completed)
-  float *scratch = nullptr;
+  b->mod_labels = b->mod_gains = b->mod_smooth = b->mod_deconv = 0;  // (until the passes below have completed)
+  float *scratch = nullptr, *scratch2 = nullptr;
   try {
-    if (np > 1) VR_HIP(vr_host::pooled_alloc(reinterpret_cast<void **>(&scratch), b->bytes, b->device));
+    if (nscratch > 0) VR_HIP(vr_host::pooled_alloc(reinterpret_cast<void **>(&scratch), b->bytes, b->device));
+    if (nscratch > 1) VR_HIP(vr_host::pooled_alloc(reinterpret_cast<void **>(&scratch2), b->bytes, b->device));
     if (gain) VR_HIP(hipMemcpy(h->d_gains, h->gains, sizeof(float) * (size_t)h->ngains, hipMemcpyHostToDevice));
     if (smooth) VR_HIP(hipMemcpy(h->d_smooth_w, wts, sizeof(wts), hipMemcpyHostToDevice));
+    if (deconv) VR_HIP(hipMemcpy(h->d_deconv_w, dwts, sizeof(dwts), hipMemcpyHostToDevice));
     VR_HIP(hipMemsetAsync(U.d_stats, 0, sizeof(vr::BufStats), U.pad_stream));
     const auto t0 = std::chrono::steady_clock::now();
     const int32_t nx = (int32_t)b->dims[0], ny = (int32_t)b->dims[1], nz = (int32_t)b->dims[2];
     const float *src = b->orig;
+    if (deconv) {  // the estimate lives where an even number of passes after it ends in ptr
+      float *u = np % 2 ? scratch : b->ptr;
+      run_deconvolution(b->orig, u, np % 2 ? b->ptr : scratch, scratch2, nx, ny, nz, daxis, dR, nda, h->d_deconv_w,
+                        h->deconv_iterations, h->deconv_floor, np ? nullptr : U.d_stats, U.pad_stream);
+      src = u;
+    }
     for (int i = 0; i < np; ++i) {
       float *dst = (np - 1 - i) % 2 ? scratch : b->ptr;  // the last pass writes ptr
       vr::BufStats *st = i == np - 1 ? U.d_stats : nullptr;
@@ -404,7 +506,8 @@ int apply_derived(vr_context *h) {
     VR_HIP(hipMemcpyAsync(U.h_stats, U.d_stats, sizeof(vr::BufStats), hipMemcpyDeviceToHost, U.pad_stream));
     VR_HIP(hipStreamSynchronize(U.pad_stream));
     if (scratch) vr_host::pooled_free(scratch, b->bytes, b->device, vr_host::Readers());
-    scratch = nullptr;
+    if (scratch2) vr_host::pooled_free(scratch2, b->bytes, b->device, vr_host::Readers());
+    scratch = scratch2 = nullptr;
     b->nonfinite = U.h_stats->nonfinite != 0;
     b->maxabs = U.h_stats->maxabs;
     b->version = next_version();
@@ -416,6 +519,7 @@ int apply_derived(vr_context *h) {
   } catch (...) {  // the buffer must not stay half written: back to the unmodified upload
     (void)hipStreamSynchronize(U.pad_stream);
     if (scratch) vr_host::pooled_free(scratch, b->bytes, b->device, vr_host::Readers());
+    if (scratch2) vr_host::pooled_free(scratch2, b->bytes, b->device, vr_host::Readers());
     vr_host::pooled_free(b->ptr, b->bytes, b->device, vr_host::Readers());
     b->ptr = b->orig;
     b->orig = nullptr;
@@ -427,6 +531,7 @@ int apply_derived(vr_context *h) {
   b->mod_labels = kl;
   b->mod_gains = kg;
   b->mod_smooth = ks;
+  b->mod_deconv = kd;
   return bad;
 }
 

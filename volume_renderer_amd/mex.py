@@ -574,6 +574,92 @@ def smooth_host(src, sigma) -> np.ndarray:
     return out.reshape(s.shape, order="F")
 
 
+DECONV_FLOOR = np.float32(1e-6)  # the default floor of 'set_deconvolution'
+
+
+def deconvolution_sigma(sigma):
+    """A PSF sigma as three singles along dims[0..2] of Data, as smoothing_sigma()."""
+    try:
+        return smoothing_sigma(sigma)
+    except _lib.VrError:
+        raise _lib.VrError(1, "set_deconvolution: sigma must be a real scalar or 3-vector, [] or false") from None
+
+
+def _deconvolution_count(iterations) -> int:
+    a = np.asarray(iterations)
+    if a.size != 1 or a.dtype.kind not in "fiu" or not np.isfinite(a.reshape(-1)[0]) or \
+            float(a.reshape(-1)[0]) != int(a.reshape(-1)[0]):
+        raise _lib.VrError(1, "set_deconvolution: iterations must be an integer scalar in 0..64")
+    n = int(a.reshape(-1)[0])
+    if n < 0 or n > _lib.VR_DECONV_MAX_ITERATIONS:
+        raise _lib.VrError(1, "set_deconvolution: iterations must be an integer scalar in 0..64")
+    return n
+
+
+def _deconvolution_floor(floor) -> float:
+    if floor is None:
+        return float(DECONV_FLOOR)
+    a = np.asarray(floor)
+    if a.size != 1 or a.dtype.kind not in "fiu":
+        raise _lib.VrError(1, "set_deconvolution: floor must be a real scalar greater than 0")
+    return float(np.float32(a.reshape(-1)[0]))  # (the library checks the value)
+
+
+def set_deconvolution(handle, sigma, iterations=0, floor=None) -> None:
+    """vr_set_deconvolution: Richardson-Lucy deconvolution of the handle's resident emission volume with a
+    Gaussian PSF of `sigma` voxels (deconvolution_sigma()), `iterations` in 0..64, `floor` (default 1e-6
+    single) under the division; None / False / [] / zeros as sigma, or 0 iterations, clear it."""
+    a = deconvolution_sigma(sigma)
+    check(lib().vr_set_deconvolution(_handle(handle), a.ctypes.data, _deconvolution_count(iterations),
+                                     _deconvolution_floor(floor)))
+
+
+def get_deconvolution(handle):
+    """vr_get_deconvolution: (sigma [3] single, iterations, floor) as set; (zeros, 0, 0.0): none."""
+    sg = np.zeros(3, np.float32)
+    n = ctypes.c_int32(0)
+    fl = ctypes.c_float(0.0)
+    check(lib().vr_get_deconvolution(_handle(handle), sg.ctypes.data, ctypes.byref(n), ctypes.byref(fl)))
+    return sg, int(n.value), np.float32(fl.value)
+
+
+def deconvolve_host(src, sigma, iterations, floor=None) -> np.ndarray:
+    """vr_deconvolve_host: the deconvolution's value rule on the CPU -- src single with at most 3 dimensions
+    (column-major: axis j of the array is dims[j]); shaped like src."""
+    s = np.asarray(src, dtype=np.float32)
+    if s.ndim > 3:
+        raise _lib.VrError(1, "deconvolve_host: src must have at most 3 dimensions")
+    dims = (ctypes.c_uint64 * 3)(*(list(s.shape) + [1] * (3 - s.ndim)))
+    sf = np.ascontiguousarray(s.reshape(-1, order="F"))
+    a = deconvolution_sigma(sigma)
+    out = np.empty(sf.size, np.float32)
+    check(lib().vr_deconvolve_host(sf.ctypes.data, dims, a.ctypes.data, _deconvolution_count(iterations),
+                                   _deconvolution_floor(floor), out.ctypes.data))
+    return out.reshape(s.shape, order="F")
+
+
+def deconv_axis_device(d_src: int, d_dst: int, dims, axis: int, d_weights: int, radius: int, epi: int, d_aux: int = 0,
+                       floor=DECONV_FLOOR, flags: int = 0, d_stats: int = 0, stream: int = 0) -> None:
+    """vr_deconv_axis_device: one filter pass with an epilogue of the deconvolution (_lib.VR_EPI_*) between
+    padded device buffers (measurements); d_aux may be d_dst for the update."""
+    d = (ctypes.c_uint64 * 3)(*(int(x) for x in dims))
+    check(lib().vr_deconv_axis_device(ctypes.c_void_p(int(d_src)), ctypes.c_void_p(int(d_dst)), d, int(axis),
+                                      ctypes.c_void_p(int(d_weights)), int(radius), int(epi),
+                                      ctypes.c_void_p(int(d_aux)) if d_aux else None, float(floor), int(flags),
+                                      ctypes.c_void_p(int(d_stats)) if d_stats else None,
+                                      ctypes.c_void_p(int(stream)) if stream else None))
+
+
+def deconv_pointwise_device(d_src: int, d_dst: int, dims, epi: int, d_aux: int, floor=DECONV_FLOOR, flags: int = 0,
+                            stream: int = 0) -> None:
+    """vr_deconv_pointwise_device: the ratio or the update as an elementwise launch over padded device
+    buffers (measurements)."""
+    d = (ctypes.c_uint64 * 3)(*(int(x) for x in dims))
+    check(lib().vr_deconv_pointwise_device(ctypes.c_void_p(int(d_src)), ctypes.c_void_p(int(d_dst)), d, int(epi),
+                                           ctypes.c_void_p(int(d_aux)), float(floor), int(flags),
+                                           ctypes.c_void_p(int(stream)) if stream else None))
+
+
 def smooth_fused_device(d_src: int, d_dst: int, dims, d_weights: int, radius, d_stats: int = 0, stream: int = 0) -> None:
     """vr_smooth_fused_device: the fused launch between two padded device buffers (measurements); d_weights
     3 x 25 floats, radius three ints."""
@@ -591,6 +677,14 @@ def read_emission(handle, offset: int, count: int) -> np.ndarray:
     out = np.empty(int(count), np.float32)
     check(lib().vr_debug_read_emission(_handle(handle), int(offset), int(count), out.ctypes.data))
     return out
+
+
+def emission_version(handle) -> int:
+    """vr_debug_emission_version: the upload version of the handle's resident emission buffer (every upload
+    and every derivation takes a new one; 0: no buffer)."""
+    v = ctypes.c_uint64(0)
+    check(lib().vr_debug_emission_version(_handle(handle), ctypes.byref(v)))
+    return int(v.value)
 
 
 def derive_times(handle):
@@ -902,7 +996,7 @@ def _group_devices():
 def volumeRender(cmd, *args):
     """The `volumeRender` mex: commands 'new', 'delete', 'mem_info', 'sync_volumes', 'render' (and
     'render_stereo', 'render_channels', 'render_projection', 'render_isosurface', 'render_transfer',
-    'render_slice', 'volume_histogram', 'set_clip', 'sync_labels', 'set_label_gains', 'set_smoothing', which the reference does
+    'render_slice', 'volume_histogram', 'set_clip', 'sync_labels', 'set_label_gains', 'set_smoothing', 'set_deconvolution', which the reference does
     not have)."""
     nrhs = 1 + len(args)
     if not isinstance(cmd, str) or len(cmd) >= 64:
@@ -999,6 +1093,27 @@ def volumeRender(cmd, *args):
                     sg.size not in (1, 3) or sg.size != max(sg.shape, default=1))):
                 raise _lib.VrError(1, "set_smoothing: sigma must be a single or double scalar or 3-vector, [] or false")
         set_smoothing(args[0], sg)
+        return None
+    if cmd == "set_deconvolution":
+        # ('set_deconvolution', h, sigma, iterations[, floor]): sigma a single or double scalar or 3-vector,
+        # iterations an integer-valued real scalar in 0..64, floor a single or double scalar (default 1e-6
+        # single); [] / false as sigma, or iterations = 0, clears
+        if nrhs < 3:
+            raise _lib.VrError(1, "insufficient parameter!")
+        if nrhs > 5:
+            raise _lib.VrError(1, "set_deconvolution: too many input arguments")
+        sg = args[1]
+        cleared = sg is None or _is_false(sg) or np.asarray(sg).size == 0
+        if not cleared:
+            sg = np.asarray(sg)
+            if sg.dtype not in (np.float32, np.float64) or sg.ndim > 2 or sg.size not in (1, 3) or \
+                    sg.size != max(sg.shape, default=1):
+                raise _lib.VrError(1, "set_deconvolution: sigma must be a single or double scalar or 3-vector, [] or false")
+        if nrhs < 4 and not cleared:
+            raise _lib.VrError(1, "set_deconvolution: iterations is missing")
+        if nrhs > 4 and np.asarray(args[3]).dtype not in (np.float32, np.float64):
+            raise _lib.VrError(1, "set_deconvolution: floor must be a real scalar greater than 0")
+        set_deconvolution(args[0], None if cleared else sg, args[2] if nrhs > 3 else 0, args[3] if nrhs > 4 else None)
         return None
     if cmd == "render_stereo":  # fused stereo pair (vr_render_stereo): args as 'render' + base
         ra, keep = render_args(*args[1:10])

@@ -101,6 +101,13 @@ class VolumeRender:
         # render whenever it differs from what the handle holds (_apply_labels).
         self.Smoothing = np.zeros(3, dtype=np.float32)
         object.__setattr__(self, "_smoothing_applied", np.zeros(3, dtype=np.float32))
+        # Richardson-Lucy deconvolution (vr_set_deconvolution): (sigma, iterations) or (sigma, iterations,
+        # floor) -- the Gaussian PSF's sigma in voxels along the three dimensions of VolumeEmission.Data (a
+        # scalar for all three), 0..64 iterations, the floor under the division (default 1e-6); False: none.
+        # The emission volume on the device is the deconvolved Data (then smoothed, times the label gains),
+        # without another upload.  Sent before a render whenever it differs from what the handle holds.
+        self.Deconvolution = False
+        object.__setattr__(self, "_deconvolution_applied", False)
         if VolumeRender._default_reflection is None:
             VolumeRender._default_reflection = Volume(1)
         # observable properties: defaults are assigned without firing the listener
@@ -170,6 +177,24 @@ class VolumeRender:
                 raise TypeError("Smoothing must be a sigma in voxels: a scalar or a 3-vector")
             val = val.reshape(-1).astype(np.float32)
             val = np.repeat(val, 3) if val.size == 1 else val.copy()
+        elif name == "Deconvolution":
+            if val is None or _is_logical(val) and not val or (len(val) == 0 if isinstance(val, (tuple, list))
+                                                                else np.size(val) == 0):
+                val = False
+            else:
+                if not isinstance(val, (tuple, list)) or len(val) not in (2, 3):
+                    raise TypeError("Deconvolution must be (sigma, iterations), (sigma, iterations, floor) or False")
+                sg = np.asarray(val[0])
+                if sg.dtype.kind not in "fiu" or sg.size not in (1, 3) or sg.size != max(sg.shape, default=1):
+                    raise TypeError("Deconvolution: sigma must be a scalar or a 3-vector, in voxels")
+                sg = sg.reshape(-1).astype(np.float32)
+                sg = np.repeat(sg, 3) if sg.size == 1 else sg.copy()
+                if np.size(val[1]) != 1 or float(val[1]) != int(val[1]) or not 0 <= int(val[1]) <= 64:
+                    raise TypeError("Deconvolution: iterations must be an integer in 0..64")
+                fl = np.float32(1e-6) if len(val) == 2 else np.float32(val[2])
+                if not (np.isfinite(fl) and fl > 0):
+                    raise TypeError("Deconvolution: floor must be finite and greater than 0")
+                val = (sg, int(val[1]), fl) if int(val[1]) > 0 and sg.any() else False
         object.__setattr__(self, name, val)
         if name in _VOLUME_PROPS and isinstance(val, Volume):
             val.TimeLastUpdate = timestamp()
@@ -206,7 +231,16 @@ class VolumeRender:
     def _apply_labels(self) -> None:
         """'sync_labels' if VolumeLabels changed since the last one (assigned, or a Volume's
         TimeLastUpdate moved), 'set_label_gains' if LabelGains differs from what the handle holds; before
-        them 'set_smoothing' if Smoothing differs from what the handle holds."""
+        them 'set_deconvolution' and 'set_smoothing' if Deconvolution or Smoothing differ from what the
+        handle holds."""
+        dc, was = self.Deconvolution, self._deconvolution_applied
+        if (dc is False) != (was is False) or (dc is not False and not (
+                np.array_equal(dc[0], was[0]) and dc[1] == was[1] and dc[2] == was[2])):
+            if dc is False:
+                volumeRender("set_deconvolution", self.objectHandle, False)
+            else:
+                volumeRender("set_deconvolution", self.objectHandle, dc[0], np.float64(dc[1]), dc[2])
+            object.__setattr__(self, "_deconvolution_applied", dc)
         if not np.array_equal(self.Smoothing, self._smoothing_applied):
             volumeRender("set_smoothing", self.objectHandle, self.Smoothing)
             object.__setattr__(self, "_smoothing_applied", self.Smoothing.copy())
