@@ -216,8 +216,10 @@ int vr_sum_channels_device(const float *d_in, int32_t n, int32_t views, uint64_t
  * d_steps[5..6] += wave sample iterations, of which any lane shaded; d_steps[7] += empty-space
  * probe runs leaped; d_steps[8..39] histogram of the box volume (floats, bins of
  * 256, last bin open) of chunks that fell back to global memory; d_steps[40..43] staged chunks with
- * S = 32, 16, 8, 4; d_steps[44] += probes that found data; d_steps[45] += floats staged into LDS.
- * [2..45] are filled by the LDS-staged kernel only. */
+ * S = 32, 16, 8, 4; d_steps[44] += probes that found data; d_steps[45] += floats staged into LDS;
+ * d_steps[46] += chunks leaped on the occupancy map's word, without a copy; d_steps[47] |= 1 << (ex mod 4)
+ * for the row length ex of every staged box (a bit set, not a count).
+ * [2..47] are filled by the LDS-staged kernel only. */
 #define VR_NUM_COUNTERS 48
 int vr_render_device(vr_context *h, const vr_render_args *args, const vr_partition *part,
                      float *d_out, unsigned long long *d_steps, void *stream);

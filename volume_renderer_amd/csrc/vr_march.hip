@@ -139,6 +139,7 @@ __device__ __forceinline__ void first_of_group(float flagf, float t0, const f3 &
 
 struct ChunkStats {
   uint32_t staged, leap, fall, iter, lit, probe, probe_fail;
+  uint32_t exmod;  // bit ex mod 4 for every box the wave staged (d_steps[47])
 };
 
 #ifndef VR_PARK_SAMPLES
@@ -700,6 +701,7 @@ __device__ __forceinline__ void march(const RenderParams &P, float *L, int lane,
       if (staged && !partial && ps == 0)
         empty = box_bricks_empty(kp, B.rx, B.ry, B.rz, B.ex, B.ey, B.ez, lane) > 0;
     }
+    if (COUNT && staged && !empty) C.exmod |= 1u << (B.ex & 3);  // row lengths mod 4 of the staged boxes
     if (COUNT && lane == 0) {  // diagnostics: box volume of partial/failed chunks, S of staged ones
       if (!staged || partial) atomicAdd(P.steps + 8 + min(box_vol >> 8, 31), 1ull);
       else atomicAdd(P.steps + 40 + (S >= 32 ? 0 : (S >= 16 ? 1 : (S >= 8 ? 2 : 3))), 1ull);
@@ -1043,6 +1045,7 @@ __global__ __launch_bounds__(64 * VR_WG_WAVES, march_min_eu(CAP, SCHED)) void ma
       atomicAdd(P.steps + 6, (unsigned long long)C.lit);
       atomicAdd(P.steps + 7, (unsigned long long)C.probe);
       atomicAdd(P.steps + 44, (unsigned long long)C.probe_fail);
+      if (C.exmod) atomicOr(P.steps + 47, (unsigned long long)C.exmod);
     }
   }
 }

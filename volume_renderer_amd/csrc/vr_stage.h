@@ -10,16 +10,12 @@
 
 #include "vr_device.h"
 #include "vr_sampling.h"
+#include "vr_stage_map.h"
 #include "vr_udiv.h"
 
 namespace vr {
 
-#ifndef VR_UDIV_MAGIC
-// 1 (round 15): the staging copy's per-lane quotients by the wave-uniform box extents (stage_box) as
-// udiv_small, the magics from a table in constant memory (one scalar load each); 0 (A/B, tests):
-// the compiler's u32 division sequences
-#define VR_UDIV_MAGIC 1
-#endif
+// (VR_UDIV_MAGIC: vr_stage_map.h)
 static __constant__ const UdivTab udiv_tab = make_udiv_tab();
 
 // Wave slot sizes (floats).  The march kernel is built for both and the host picks per frame
@@ -317,79 +313,85 @@ __device__ __forceinline__ bool stage_box_elems(float *L, const DevTex &t, const
   return __any(nz);
 }
 
-// Copy box B of the apron volume into the wave's LDS slot (row-major, x fastest).  A wave pass
-// moves 64 / ex whole rows (lane -> (row slot, x)); row offsets advance incrementally, relative to
-// a wave-uniform base pointer, so a pass costs a handful of adds instead of per-element 64-bit
-// index products.  Returns whether any staged voxel is non-zero (NaN counts as non-zero), for
-// the whole wave.
-template <bool BIG>
-__device__ __forceinline__ bool stage_box(float *L, const DevTex &t, const Box &B, int lane) {
-  const int ex = B.ex, ey = B.ey;
-  const int rows = ey * B.ez;
-  // (32-bit byte offsets overflow; rows: the bound of udiv_small's dividend below, which no slot's box
-  // reaches)
-  if (ex > 64 || (!BIG && (uint64_t)t.pxy * (uint64_t)B.ez * 4u >= 0xFFFFFFFFull) ||
-      (VR_UDIV_MAGIC && rows > (int)UDIV_MAX_N - 64))
-    return stage_box_elems(L, t, B, lane);
+// stage_box's copy with V floats of a row per lane (V = 4, 2 or 1 <= ex <= 64): the lane map, the pass
+// count and the advance from pass to pass are vr_stage_map.h's.  A lane's V floats come in one load
+// from an address that is only 4-byte aligned (a row starts anywhere) and go to the slot's dense rows
+// as dword stores at immediate offsets from one address.  The last group of a row starts at ex - V, so
+// it overlaps its neighbour when ex is no multiple of V: the same values to the same slot words, the OR
+// below unaffected, and no lane reads beyond its own row -- nothing outside the padded volume.
+template <int V>
+struct StageVec {
+  typedef float type __attribute__((ext_vector_type(V), aligned(4)));
+};
+template <>
+struct StageVec<1> {
+  typedef float type;
+};
+template <bool BIG, int V>
+__device__ __forceinline__ bool stage_box_rows(float *L, const DevTex &t, const Box &B, int lane) {
   typedef typename std::conditional<BIG, uint64_t, uint32_t>::type off_t;
-#if VR_UDIV_MAGIC
-  // The lane's row slot, x, y, z and pass count: quotients by the wave-uniform ex, 64 / ex and ey as
-  // udiv_small, the magics from one scalar load each.  Dividends: 64, lane and rr are at most 64; the
-  // rounded-up row count is below rows + 64, and rows * ex <= the slot size (2560 floats at most), so
-  // it is below 4096 -- a box of more rows (no slot holds one) takes the element-wise copy above.  ey
-  // may exceed 64 (a narrow box): rr < 64 then has the quotient 0 by 64 as well.
-  const UdivEntry ue = udiv_tab.e[ex];
-  const uint32_t mey = udiv_tab.e[min(ey, 64)].m;
-  const int per = (int)((64u * ue.m) >> UDIV_SHIFT);  // rows per pass (wave-uniform, SALU)
-  const int rr = (int)udiv_small((uint32_t)lane, ue.m), xr = (int)urem_small((uint32_t)lane, (uint32_t)rr, (uint32_t)ex);
-  // passes with a row for this lane
-  const int n = rr < per ? (int)udiv_small((uint32_t)(rows - rr + per - 1), ue.mper) : 0;
-  const int z = (int)udiv_small((uint32_t)rr, mey);
-  int y = (int)urem_small((uint32_t)rr, (uint32_t)z, (uint32_t)ey);
-#else
-  const int per = 64 / ex;  // rows per pass (wave-uniform)
-  const int rr = lane / ex, xr = lane - rr * ex;
-  const int n = rr < per ? (rows - rr + per - 1) / per : 0;  // passes with a row for this lane
-  int y = rr % ey;
-  const int z = rr / ey;
-#endif
+  typedef typename StageVec<V>::type vec_t;
+  const uint32_t ey = (uint32_t)B.ey;
+  const uint32_t rows = ey * (uint32_t)B.ez;
+  const StageMap M = stage_map<V>((uint32_t)B.ex, ey, udiv_tab);  // (wave-uniform: SALU and scalar loads)
+  const StageLane s = stage_lane<V>(M, (uint32_t)lane, rows);
   const char *base = reinterpret_cast<const char *>(
       t.p + ((uint64_t)B.rz * t.pxy + (uint64_t)B.ry * t.px + (uint64_t)B.rx));  // uniform
-  off_t g = ((off_t)z * t.pxy + (off_t)y * t.px + (off_t)xr) * 4u;               // bytes
-  const off_t g_row = (off_t)per * t.px * 4u;
-  const off_t g_wrap = ((off_t)t.pxy - (off_t)ey * t.px) * 4u;
-  int l = z * B.pxy + y * B.px + xr;  // slot word
-  const int l_row = per * B.px;
-  const int l_wrap = B.pxy - ey * B.px;  // plane padding (0 for dense pitches)
+  off_t g = ((off_t)s.z * t.pxy + (off_t)s.y * t.px + (off_t)s.x) * 4u;       // bytes
+  int32_t l = (int32_t)(s.z * (uint32_t)B.pxy + s.y * (uint32_t)B.px + s.x);     // slot word
+  uint32_t y = s.y;
+  const StageStep<off_t> T = stage_step<off_t>(M, (off_t)t.px, (off_t)t.pxy, (off_t)4u, B.px, B.pxy);
+  const int n = (int)s.n;
   uint32_t acc = 0;
   for (int k0 = 0; k0 < n; k0 += VR_STAGE_UNROLL) {
-    float v[VR_STAGE_UNROLL];
+    vec_t v[VR_STAGE_UNROLL];
     int li[VR_STAGE_UNROLL];
 #pragma unroll
     for (int j = 0; j < VR_STAGE_UNROLL; ++j) {
       li[j] = l;
-      if (k0 + j < n) {
-        const float *src = reinterpret_cast<const float *>(base + g);
-        v[j] = *src;
-      }
-      l += l_row;
-      g += g_row;
-      y += per;
-      while (y >= ey) {
-        y -= ey;
-        g += g_wrap;
-        l += l_wrap;
-      }
+      if (k0 + j < n) v[j] = *reinterpret_cast<const vec_t *>(base + g);
+      stage_next(M, T, g, l, y);
     }
 #pragma unroll
     for (int j = 0; j < VR_STAGE_UNROLL; ++j) {
       if (k0 + j < n) {
-        L[li[j]] = v[j];
-        acc |= __float_as_uint(v[j]);
+        if constexpr (V == 1) {
+          L[li[j]] = v[j];
+          acc |= __float_as_uint(v[j]);
+        } else {
+#pragma unroll
+          for (int e = 0; e < V; ++e) {
+            L[li[j] + e] = v[j][e];
+            acc |= __float_as_uint(v[j][e]);
+          }
+        }
       }
     }
   }
   return __any((acc & 0x7fffffffu) != 0u);  // (the sign bit masked once, after the OR: -0 is empty)
+}
+
+#ifndef VR_STAGE_VEC
+// Floats per lane of the staging copy (round 24): 4, 2 or 1 (A/B, tests: the copy of rounds 1-15).  A
+// box narrower than the width takes the next narrower one.
+#define VR_STAGE_VEC 4
+#endif
+// Copy box B of the apron volume into the wave's LDS slot (row-major, x fastest).  A wave pass
+// moves 64 / ceil(ex / V) whole rows (lane -> (row slot, x group)); row offsets advance incrementally,
+// relative to a wave-uniform base pointer, so a pass costs a handful of adds instead of per-element
+// 64-bit index products.  Returns whether any staged voxel is non-zero (NaN counts as non-zero), for
+// the whole wave.
+template <bool BIG>
+__device__ __forceinline__ bool stage_box(float *L, const DevTex &t, const Box &B, int lane) {
+  // (32-bit byte offsets overflow; rows: the bound of udiv_small's dividend (vr_stage_map.h), which no
+  // slot's box reaches -- rows * ex <= the slot size, 2560 floats at most)
+  if (B.ex > 64 || (!BIG && (uint64_t)t.pxy * (uint64_t)B.ez * 4u >= 0xFFFFFFFFull) ||
+      (VR_UDIV_MAGIC && B.ey * B.ez > (int)UDIV_MAX_N - 64))
+    return stage_box_elems(L, t, B, lane);
+  const int w = stage_width((uint32_t)B.ex, VR_STAGE_VEC);  // (wave-uniform)
+  if (VR_STAGE_VEC >= 4 && w == 4) return stage_box_rows<BIG, 4>(L, t, B, lane);
+  if (VR_STAGE_VEC >= 2 && w == 2) return stage_box_rows<BIG, 2>(L, t, B, lane);
+  return stage_box_rows<BIG, 1>(L, t, B, lane);
 }
 
 // Chunk set-up: the box of every tap the wave's live rays take in their next S samples, S halved
